@@ -11,11 +11,19 @@ as rescore.py computes them once per weight.
 Every rank scores its own U utterances (weak scaling; utterances are independent).
 ``--workload c4``: BASELINE config C4 instead — the full 7176-utterance real-length set at N=100
 (alfred test length histogram), one fixed set split over the ranks (strong scaling).
-The default C3 run also reports ``c4_secondary``: one pass of that full C4 set on rank 0 at N=1.
+The default C3 run with ``--full`` also reports ``c4_secondary``: one pass of that full C4 set on rank 0 at N=1.
 
-Prints ONE JSON line on rank 0.  Extra legs (not in the timed region): a HIP-event
-per-kernel-kind profile pass (roofline of the dominant kernel) and a bounded CPU
-baseline (the oracle's PyTorch-CPU restatement of the reference work pattern).
+Prints ONE JSON line on rank 0.  A plain run sets up (synthetic set, weights, the MLM fine-tune
+that produces the scored checkpoint), warms up, times ``--steps`` steps and prints the line.
+``--dump-outputs DIR`` also writes what the last timed step returned (``lm.npy``: the float64 PLL
+of every hypothesis of the global set in set order; ``argmax.npy``: rank 0's fused argmax
+[101 weights, utterances] as float64); the inputs are seeded, so two builds run with the same
+arguments can be compared output for output.
+``--full`` adds the legs outside the timed region: a HIP-event per-kernel-kind profile pass
+(roofline of the dominant kernel), the reranked-CER check against the oracle's fusion, a bounded
+CPU baseline (the oracle's PyTorch-CPU restatement of the reference work pattern), the
+reduced-precision fp16 leg and the C4 secondary pass.  --cpu-seconds, --no-profile, --fp16-steps
+and --c4-secondary shape those legs and have no effect without --full.
 """
 from __future__ import annotations
 
@@ -150,13 +158,18 @@ def main():
     ap.add_argument("--utts", type=int, default=200, help="utterances per rank per step (C3: 200)")
     ap.add_argument("--nbest", type=int, default=50)
     ap.add_argument("--max-rows", type=int, default=262144, help="token rows per launch chunk (262144: +0.5 %% over 131072)")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="CPU-baseline budget (0 = skip)")
-    ap.add_argument("--no-profile", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs outside the timed region: per-kernel profile / roofline, rerank check "
+                         "against the oracle, CPU baseline, fp16 leg, C4 secondary pass (off: steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/lm.npy and DIR/argmax.npy")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="--full: CPU-baseline budget (0 = skip)")
+    ap.add_argument("--no-profile", action="store_true", help="--full: skip the per-kernel profile pass")
     ap.add_argument("--precision", default="fp16x3", choices=("fp16x3", "fp16"),
                     help="fp16x3 (default): split-fp16 operands, fp32-accurate (the reference computes "
                          "in fp32); fp16: fp16 operands (reduced precision, reported as a secondary field)")
     ap.add_argument("--fp16-steps", type=int, default=2,
-                    help="secondary leg: steps of the reduced-precision fp16 mode (0 = skip)")
+                    help="--full: steps of the reduced-precision fp16 leg (0 = skip)")
     ap.add_argument("--force-gather", action="store_true",
                     help="at one rank too: a one-rank nccl (RCCL) group and the all_gather inside every step")
     ap.add_argument("--finetune-steps", type=int, default=300,
@@ -167,7 +180,7 @@ def main():
                     help="c3 (default): U utterances x N=50 per rank (weak scaling); c4: the full 7176 x N=100 "
                          "real-length set split over the ranks (strong scaling)")
     ap.add_argument("--c4-secondary", type=int, default=1,
-                    help="C3 runs, rank 0 at N=1: one timed pass of the full C4 set (0 = skip)")
+                    help="--full, C3 runs, rank 0 at N=1: one timed pass of the full C4 set (0 = skip)")
     args = ap.parse_args()
 
     # --gpus N without a launcher: N fresh rank processes (one per GPU) before any GPU call here;
@@ -270,11 +283,12 @@ def main():
             out = shard.gather_scores(pair.cpu(), counts).to(dev)
         else:
             out = shard.gather_scores(pair, counts) if gather else pair
+        arg = None
         if rank == 0:
-            rerank.fuse_rerank(out[0], out[1], hyp_len_all, nb_all.utt_off, grid, "norm", args.nbest, local)
-        return out[1]
+            arg = rerank.fuse_rerank(out[0], out[1], hyp_len_all, nb_all.utt_off, grid, "norm", args.nbest, local)
+        return out[1], arg
 
-    lm = None
+    lm = arg_last = None
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
@@ -283,7 +297,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        lm = step()
+        lm, arg_last = step()
     torch.cuda.synchronize()
     if gather:
         dist.barrier()
@@ -296,10 +310,16 @@ def main():
     total_fwd = n_fwd_all * args.steps
     value = total_fwd / dt
 
+    # ---- --dump-outputs: what the last timed step returned, for build-to-build comparison ----
+    if args.dump_outputs and rank == 0 and lm is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "lm.npy"), lm.double().cpu().numpy())
+        np.save(os.path.join(args.dump_outputs, "argmax.npy"), arg_last.cpu().numpy().astype(np.float64))
+
     # ---- profile leg: per-kernel-kind HIP-event timing (separate, untimed pass) ----------
     roof = None
     kinds = {}
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         scorer.profile(True)
         scorer.score_nbest(d_tok, nb.hyp_off)
         torch.cuda.synchronize()
@@ -369,7 +389,7 @@ def main():
     # HIP fusion over the 101-weight grid + corpus CER on this step's LM scores, checked
     # against the oracle's numpy restatement of rescore.py:25-58 on the same scores.
     rr = None
-    if rank == 0:
+    if args.full and rank == 0:
         from oracle import rescore_ref as RR
         lm_np = lm.double().cpu().numpy()
         bw, bcer, arg, cers = rerank.find_best_weight(nb_all, lm_np, n_best=args.nbest, device=local)
@@ -389,7 +409,7 @@ def main():
     # Also a scoring-parity spot check at bench scale: the PLL of every sampled hypothesis
     # (reference work pattern, fp32 CPU) against the HIP lm of the timed steps.
     cpu, cpu_model = None, None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:       # the contract: rank 0 at N = 1 only
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:    # the contract: rank 0 at N = 1 only
         from oracle.bert_ref import TorchBert, set_cpu_threads
         import oracle.bert_ref as OB
         threads = set_cpu_threads()
@@ -447,7 +467,7 @@ def main():
 
     # ---- secondary leg: the reduced-precision fp16 mode on the same input (labelled) ------
     fp16 = None
-    if rank == 0 and world == 1 and args.precision != "fp16" and args.fp16_steps > 0:
+    if args.full and rank == 0 and world == 1 and args.precision != "fp16" and args.fp16_steps > 0:
         s16 = PLLScorer(weights, BERT_BASE, device=local, max_rows=args.max_rows, precision="fp16")
         lm16 = s16.score_nbest(d_tok, nb.hyp_off)
         torch.cuda.synchronize()
@@ -465,14 +485,15 @@ def main():
 
     # ---- secondary leg: BASELINE config C4 (full 7176 x N=100 real-length set) at one GPU ------
     c4 = None
-    if rank == 0 and world == 1 and args.workload == "c3" and args.c4_secondary and args.precision == "fp16x3":
+    if (args.full and rank == 0 and world == 1 and args.workload == "c3" and args.c4_secondary
+            and args.precision == "fp16x3"):
         c4 = c4_secondary(scorer, weights0, local)
 
     if rank == 0:
         mean_T = float(np.average(lens, weights=lens - 2))
         rec = {"metric": "masked-token BERT forwards/sec (MLM_PLL, N=50, L~32)", "value": round(value, 2),
                "unit": "masked fwd/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-               "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
+               "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "full": bool(args.full),
                "scaling": "strong" if args.workload == "c4" else "weak",
                "vs_baseline": None, "dtype": DTYPE[args.precision],
                "data": ("synthetic (PCG64 seed 1, permuted N-best with unsorted AM scores"

@@ -87,3 +87,19 @@ def test_bench_gpus_n_spawns_before_any_gpu_call(monkeypatch):
         bench.main()
     assert e.value.code == 0
     assert calls == [(2, ["--gpus", "2", "--steps", "1"], os.path.abspath(bench.__file__))]
+
+
+def test_bench_full_and_dump_outputs_reach_the_ranks(monkeypatch, tmp_path):
+    """--full and --dump-outputs DIR parse and are handed to the rank processes unchanged."""
+    sys.path.insert(0, REPO)
+    import bench
+    calls = []
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setattr(launch, "spawn_ranks", lambda n, argv, script=None, **k: calls.append((n, list(argv))) or 0)
+    argv = ["--gpus", "2", "--steps", "1", "--full", "--dump-outputs", str(tmp_path / "out")]
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 0
+    assert calls == [(2, argv)]
+    assert not (tmp_path / "out").exists()          # the launching parent writes nothing itself
