@@ -111,6 +111,11 @@ _DEBUG_SIGS = {
     "rs_debug_sgemm": (CI, [CI] * 3 + [P, CI, CI, P, CI, CI, P, CI, CI, P]),
     "rs_debug_sgemm_pick": (CI, [CI] * 5),
     "rs_debug_gelu": (CI, [P, P, CI, P]),
+    # (epi, A2, W2, bias, gamma, beta, eps, out, ldc, M_pad, m_valid, N, K, lnx, lncnt, lnerr, stream)
+    "rs_debug_x3s": (CI, [CI, P, P, P, P, P, ctypes.c_float, P, CI, CI, CI, CI, CI, P, P, P, P]),
+    "rs_debug_lnres_sizes": (CI, [CI, CI, ctypes.POINTER(I64)]),
+    # (qkv32, len, row, n_seq, max_len, H, heads, kx, ctx, stream)
+    "rs_debug_attention_full": (CI, [P, P, P, CI, CI, CI, CI, CI, P, P]),
 }
 EXPORTED = tuple(_SIGS)          # the shipped library's entries (include/rescore.h)
 _SIGS.update(_DEBUG_SIGS)

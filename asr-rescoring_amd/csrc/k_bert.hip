@@ -1280,6 +1280,24 @@ extern "C" int rs_debug_attention(int kind, const void* qkv, const int* len, con
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
+// Test entry (not part of the scoring path): the production attention router on fp32 Q/K/V
+// [rows, 3H] over sequences [0, n_seq) — launch_attention_full as run_chunk calls it for a
+// split-operand layer without dedup (kx = 2: ctx the interleaved two-part image [rows, 2H]).
+// max_len: the longest sequence of the launch (<= 48 / <= 64: attn16x3v2_kernel with 48 / 64 staged
+// key rows; above: the mixed chunk, attn16x3v2_kernel<64> and attn_full_kernel<float> each skipping
+// the other's sequences).  len / row: device int32 arrays.
+extern "C" int rs_debug_attention_full(const void* qkv32, const int* len, const int* row, int n_seq, int max_len,
+                                       int H, int heads, int kx, void* ctx, void* stream) {
+    if (!qkv32 || !len || !row || !ctx || n_seq <= 0 || max_len <= 0 || heads <= 0 || H != heads * 64) return -1;
+    if (kx != 2 && kx != 3) return -1;
+    SeqMeta sm{};
+    sm.len = len;
+    sm.row = row;
+    const hipError_t e = launch_attention_full(qkv32, true, sm, 0, n_seq, 0, H, heads, (f16*)ctx, kx,
+                                               (hipStream_t)stream, false, max_len);
+    return e == hipSuccess ? 0 : -2;
+}
+
 namespace {
 // memory skeleton of the two-block ln_res_rows pass: the same loads and stores per row
 // (x32 fp32, two fp16 rows, stats; x32 + fp16 image written), no arithmetic beyond a sum

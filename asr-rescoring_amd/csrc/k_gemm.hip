@@ -924,11 +924,22 @@ __device__ __forceinline__ bool lnr_next_list(const EpiArgs& ep, int& t, unsigne
     }
 }
 
-// End of a workgroup (thread 0): the last of the grid zeroes the counters for the next launch
-// (every workgroup has taken its tickets by then: each adds to LNC_DONE after its own).
-__device__ __forceinline__ void lnr_done(const EpiArgs& ep) {
+// End of a workgroup (its wave 0): the last of the grid zeroes the counters and the gang slots for
+// the next launch (every workgroup has taken its tickets and settled or read its gang's slot by
+// then: each adds to LNC_DONE after its own), so ep.lncnt is all zero after every launch, as
+// common.h documents it.  The slots are tag-matched, so a stale one is harmless until the 32-bit
+// launch sequence number wraps; zeroed, not even then.  64 lanes x 20 slots.
+__device__ __forceinline__ void lnr_done(const EpiArgs& ep, int lane) {
     unsigned* c = ep.lncnt;
-    if (lnr_add(c, LNC_DONE) + 1 != gridDim.x) return;
+    unsigned last = 0;
+    if (lane == 0) last = lnr_add(c, LNC_DONE) + 1 == gridDim.x;
+    if (!__builtin_amdgcn_readfirstlane(last)) return;
+    static_assert(LNC_TAB_N % 64 == 0, "gang slots per lane");
+    unsigned long long* tab = (unsigned long long*)c + LNC_TAB;
+#pragma unroll
+    for (int i = 0; i < LNC_TAB_N / 64; ++i)
+        __hip_atomic_store((lgu64*)(tab + lane + 64 * i), 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (lane != 0) return;
     const int w[] = {LNC_OVF, LNC_GANGS, LNC_DONE};
     for (int x = 0; x < 8; ++x) __hip_atomic_store((lgu32*)(c + LNC_LOCAL + 16 * x), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     for (int i = 0; i < 3; ++i) __hip_atomic_store((lgu32*)(c + w[i]), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -993,7 +1004,7 @@ gemm_x3s_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
     stamp(8);
     if ((unsigned)t >= (unsigned)n_tiles) {
         if constexpr (LNR) {
-            if (tid == 0) lnr_done(ep);
+            if (wave == 0) lnr_done(ep, lane);
         }
         return;
     }
@@ -1602,7 +1613,7 @@ gemm_x3s_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
         }
     }
     if constexpr (LNR) {
-        if (tid == 0) lnr_done(ep);
+        if (wave == 0) lnr_done(ep, lane);
     }
 }
 
@@ -1918,6 +1929,40 @@ extern "C" int rs_debug_gemm(int cfg, int dbg, const void* A, const void* W, con
         default: return -1;
     }
     return e == hipSuccess ? 0 : -2;
+}
+
+// Test entry (not part of the scoring path): one split-operand fp16x3 GEMM through the production
+// launcher (launch_gemm_x3s with ldw = 2K, so RS_LNGANG is honoured) in the forms the scoring path
+// uses.  A2 [M_pad, 2K], W2 [N, 2K]: interleaved two-part images.  epi EPI_BIAS_F32: out fp32
+// [M_pad, ldc] (ldc >= N: a column window of a wider buffer); EPI_GELU_F16: out the two-part image
+// [M_pad, ldc] (ldc >= 2N); EPI_LNRES_IMG: out the residual image [M_pad, 2N], rewritten in place
+// with image(LN(A.W^T + bias + out; gamma, beta, eps)), lnx / lncnt / lnerr the caller's buffers
+// (sizes: rs_debug_lnres_sizes; zeroed once by the caller), as rs_api.hip's lnres_ep passes them.
+extern "C" int rs_debug_x3s(int epi, const void* A2, const void* W2, const float* bias, const float* gamma,
+                            const float* beta, float eps, void* out, int ldc, int M_pad, int m_valid, int N, int K,
+                            void* lnx, void* lncnt, void* lnerr, void* stream) {
+    if (epi != EPI_BIAS_F32 && epi != EPI_GELU_F16 && epi != EPI_LNRES_IMG) return -1;
+    if (!A2 || !W2 || !bias || !out || N <= 0 || K <= 0 || m_valid < 0 || m_valid > M_pad) return -1;
+    if (ldc < (epi == EPI_BIAS_F32 ? N : 2 * N)) return -1;
+    EpiArgs ep{};
+    ep.bias = bias; ep.out = out; ep.ldc = ldc; ep.m_valid = m_valid; ep.kx = 1; ep.nlog = N;
+    if (epi == EPI_LNRES_IMG) {
+        if (!gamma || !beta) return -1;
+        ep.res_g = gamma; ep.res_b = beta; ep.ln_eps = eps;
+        ep.lnx = lnx; ep.lncnt = (unsigned*)lncnt; ep.lnerr = (unsigned*)lnerr;
+    }
+    const hipError_t e = launch_gemm_x3s(epi, (const f16*)A2, (const f16*)W2, 2 * K, M_pad, N, K, ep, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : -2;
+}
+
+// Test entry: the buffer sizes of one fused residual + LayerNorm GEMM launch over M_pad rows and its
+// grid — out[0] = bytes of lnx, out[1] = bytes of lncnt, out[2] = workgroups (whole gangs of N / 256).
+extern "C" int rs_debug_lnres_sizes(int M_pad, int N, long long* out) {
+    if (!out || M_pad <= 0 || M_pad % 256 || N <= 0 || N % 256) return -1;
+    out[0] = (long long)(lnres_granules(M_pad) * 8);
+    out[1] = (long long)lnres_counter_bytes();
+    out[2] = gemm_lnres_workgroups(N);
+    return 0;
 }
 
 // Test utility (not part of the scoring path): y[i] = gelu2(x[i]) — the epilogues' GELU evaluated

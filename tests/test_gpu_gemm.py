@@ -4,7 +4,14 @@
 * the persistent kernel's wave schedule (younger half at s_setprio 1 and one MFMA substep behind,
   wave-private epilogue slabs without the epilogue barrier) is BITWISE equal to the
   barrier-synchronised baseline — the same MFMA order per accumulator — on fresh random inputs
-  (a reduced race screen).
+  (a reduced race screen);
+* the split-operand fp16x3 kernel in the forms the scoring path launches it (rs_debug_x3s, the
+  production launcher): fp32 output into a column window of a wider buffer, one row panel with 1 / 37
+  valid rows, K = 256 and the 2- and 3-step K loops (K = 64, 96), against a float64 reference on
+  the values the images hold, err <= 4 max(e32, output quantisation) with e32 the error of the same
+  expression in torch fp32.  Measured err / e32 on MI355X: window 0.72, 1 / 37 rows 0.47 / 0.93;
+  fp32 output K 64 / 96 / 256 at M 256: 0.82 / 0.76 / 0.61, at M 40960: 0.74 / 0.61 / 0.60;
+  GELU image K 64 / 96 / 256 at M 256: 0.88 / 0.79 / 0.65, at M 40960: 0.83 / 0.77 / 0.66.
 """
 import ctypes
 
@@ -12,6 +19,7 @@ import pytest
 import torch
 
 from asr_rescoring_amd import _lib
+from x3s_image import _split2, _unsplit2, gemm_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -71,22 +79,6 @@ def test_persistent_schedule_bitwise(gemm, name, N, K, gelu):
         o1 = gemm(prod, 0, A, W, b, torch.full((M, N), float("nan"), device="cuda", dtype=torch.float16))
         o2 = gemm(base, 0, A, W, b, torch.full((M, N), float("nan"), device="cuda", dtype=torch.float16))
         assert torch.equal(o1.view(torch.int16), o2.view(torch.int16)), (name, rep)
-
-
-def _split2(x):
-    """The split-operand GEMM's two-part image of fp32 x [R, K] (common.h kx == 2): hi and
-    lo = (x - hi) * 64 interleaved per 32-column K-step, [hi 0..31 | lo 0..31 | hi 32..63 | ...]."""
-    hi = x.half()
-    lo = ((x - hi.float()) * 64.0).half()
-    R, K = x.shape
-    return torch.stack([hi.view(R, K // 32, 32), lo.view(R, K // 32, 32)], dim=2).reshape(R, 2 * K).contiguous()
-
-
-def _unsplit2(img):
-    """hi + lo / 64 of an interleaved two-part image [R, 2N] -> fp32 [R, N]."""
-    R, N2 = img.shape
-    v = img.float().view(R, N2 // 64, 2, 32)
-    return (v[:, :, 0] + v[:, :, 1] / 64.0).reshape(R, N2 // 2)
 
 
 def test_split2_layout():
@@ -167,3 +159,97 @@ def test_gelu_vs_torch_fp32():
     assert lib.rs_debug_gelu(bad.data_ptr(), yb.data_ptr(), 3, torch.cuda.current_stream().cuda_stream) == 0
     torch.cuda.synchronize()
     assert not torch.isfinite(yb).any(), yb
+
+
+# ---- the split-operand epilogues in the forms the scoring path launches (rs_debug_x3s) ----------
+EPI_GELU_F16, EPI_BIAS_F32 = 1, 5
+
+
+def _x3s_operands(M, N, K, seed):
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    A = torch.randn(M, K, device="cuda", generator=g)
+    W = torch.randn(N, K, device="cuda", generator=g) * 0.05
+    b = torch.randn(N, device="cuda", generator=g) * 0.1
+    return _split2(A), _split2(W), b
+
+
+def _x3s_launch(epi, A2, W2, b, out, out_off, ldc, M_pad, m_valid, N, K):
+    """out_off: element offset of the output window inside ``out``."""
+    rc = _lib.load().rs_debug_x3s(epi, A2.data_ptr(), W2.data_ptr(), b.data_ptr(), None, None, 0.0,
+                                  out.data_ptr() + out_off * out.element_size(), ldc, M_pad, m_valid, N, K,
+                                  None, None, None, torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    return rc
+
+
+def _x3s_check(name, got64, A2, W2, b, gelu, img):
+    """float64 reference on the values the images hold; yardstick e32 = the same expression in torch
+    fp32.  err <= 4 max(e32, q max|y|), q the output format's own quantisation doubled: 2^-21 for
+    the two-part image, 2^-23 for fp32."""
+    ref, r32 = gemm_ref(A2, W2, b, torch.float64), gemm_ref(A2, W2, b, torch.float32)
+    if gelu:
+        ref, r32 = torch.nn.functional.gelu(ref), torch.nn.functional.gelu(r32)
+    ref, r32 = ref[:got64.shape[0]], r32[:got64.shape[0]]
+    e32 = (r32.double() - ref).abs().max().item()
+    err = (got64 - ref).abs().max().item()
+    bound = 4 * max(e32, 2.0 ** (-21 if img else -23) * ref.abs().max().item())
+    print(f"X3S {name}: err {err:.3e} e32 {e32:.3e} err/e32 {err / max(e32, 1e-300):.2f} err/bound {err / bound:.3f}")
+    assert torch.isfinite(got64).all(), name
+    assert err <= bound, (name, err, e32, bound)
+
+
+def test_x3s_bias_f32_column_window():
+    """The last layer's K/V-only GEMM: N = 512 written at column offset 256 of an ldc = 768 fp32
+    buffer; the other 256 columns keep their NaN sentinel bitwise."""
+    M, N, K, ldc = 512, 512, 768, 768
+    A2, W2, b = _x3s_operands(M, N, K, 21)
+    sentinel = torch.tensor([0x7FC12345], dtype=torch.int32, device="cuda").view(torch.float32)
+    buf = sentinel.expand(M, ldc).contiguous()
+    assert _x3s_launch(EPI_BIAS_F32, A2, W2, b, buf, 256, ldc, M, M, N, K) == 0
+    assert (buf[:, :256].contiguous().view(torch.int32) == 0x7FC12345).all()
+    _x3s_check("window", buf[:, 256:].double(), A2, W2, b, False, False)
+
+
+@pytest.mark.parametrize("m_valid", [1, 37])
+def test_x3s_bias_f32_few_valid_rows(m_valid):
+    """The dense scored-query GEMM: one 256-row panel of which 1 / 37 rows are sequences."""
+    M, N, K = 256, 768, 768
+    A2, W2, b = _x3s_operands(M, N, K, 22)
+    A2[m_valid:] = 0
+    out = torch.full((M, N), float("nan"), device="cuda")
+    assert _x3s_launch(EPI_BIAS_F32, A2, W2, b, out, 0, N, M, m_valid, N, K) == 0
+    _x3s_check(f"few{m_valid}", out[:m_valid].double(), A2, W2, b, False, False)
+
+
+# K = 64 and 96 (2 and 3 K-steps; no model reaches them, launch_gemm_x3s accepts them) are in range
+# by the kernel's code: the prologue stages step 0, step kt issues step kt + 1's DMA into the buffer
+# step kt - 1 used (behind step kt's barrier) and the last step issues none, so nk = 2 runs exactly
+# one in-loop DMA; the transition uses "the buffer step nk - 2 used" ((par + nk - 1) & 1) ^ 1, which
+# exists for nk >= 2 and is behind the last step's barrier, and the next tile starts at par = that
+# buffer, so an odd nk (96 / 32 = 3) only alternates the starting buffer per tile.  M = 256 * 160 with
+# N = 512 gives 320 tiles on at most 256 workgroups: tile transitions at both parities.
+@pytest.mark.parametrize("M", [256, 256 * 160])
+@pytest.mark.parametrize("K", [64, 96, 256])
+@pytest.mark.parametrize("epi", [EPI_BIAS_F32, EPI_GELU_F16])
+def test_x3s_small_k(epi, K, M):
+    """K = 256, the smallest K the product reaches (hidden 256), and the 2- and 3-step K loops."""
+    N = 512
+    A2, W2, b = _x3s_operands(M, N, K, 23 + K)
+    if epi == EPI_BIAS_F32:
+        out = torch.full((M, N), float("nan"), device="cuda")
+        assert _x3s_launch(epi, A2, W2, b, out, 0, N, M, M, N, K) == 0
+        got = out.double()
+    else:
+        out = torch.full((M, 2 * N), float("nan"), device="cuda", dtype=torch.float16)
+        assert _x3s_launch(epi, A2, W2, b, out, 0, 2 * N, M, M, N, K) == 0
+        got = _unsplit2(out, torch.float64)
+    _x3s_check(f"smallk-epi{epi}-K{K}-M{M}", got, A2, W2, b, epi == EPI_GELU_F16, epi == EPI_GELU_F16)
+
+
+def test_x3s_rejects_k_below_two_steps():
+    """K = 32 (one K-step) and K % 32 != 0 are refused by the launcher; the output is untouched."""
+    A2, W2, b = _x3s_operands(256, 256, 64, 29)
+    out = torch.full((256, 256), float("nan"), device="cuda")
+    for K in (32, 48, 0):
+        assert _x3s_launch(EPI_BIAS_F32, A2, W2, b, out, 0, 256, 256, 256, 256, K) != 0
+    assert torch.isnan(out).all()
