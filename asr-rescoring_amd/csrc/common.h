@@ -146,7 +146,8 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 
 // ---- launchers (defined in k_gemm.hip / k_bert.hip / k_rerank.hip) ---------------------
-// tag != 0: the same kernel instantiated under a distinct VAR tag bit (kernel name only), so
+// tag != 0: the same kernel instantiated under a name-tag option (k_gemm.hip P_TAG_OPROJ /
+// P_TAG_FFN2; the kernel name only, besides RS_GEMM_GROUP_M_FFN2 for tag 2), so
 // rocprofv3 separates the O-projection (tag 1) and BertOutput (tag 2) launches from the QKV
 // launches of the same epilogue
 hipError_t launch_gemm(int epi, const f16* A, const f16* W, int M_pad, int N_pad, int K,

@@ -56,11 +56,11 @@ __device__ __forceinline__ unsigned mix_lo2(unsigned hi2, float x0x64, float x1x
     return d;
 }
 
-// 16-byte epilogue store; VAR&64: non-temporal (streamed past L2, keeps the A panels there)
-template <int VAR>
+// 16-byte epilogue store; NT: non-temporal (streamed past L2, keeps the A panels there)
+template <bool NT>
 __device__ __forceinline__ void st16(uint4* p, uint4 v) {
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    if constexpr (VAR & 64) __builtin_nontemporal_store((u32x4){v.x, v.y, v.z, v.w}, (u32x4*)p);
+    if constexpr (NT) __builtin_nontemporal_store((u32x4){v.x, v.y, v.z, v.w}, (u32x4*)p);
     else *p = v;
 }
 

@@ -33,6 +33,26 @@
 
 namespace {
 
+// Kernel options: the `int OPT` template argument of gemm_persist_kernel (P_*) and gemm_x3s_kernel
+// (X_*), OR-ed together by the launchers.  (gemm_f16_kernel has none: what varies there follows
+// from its epilogue.)  The values appear in the mangled kernel names; tools/pmc_mfma.py and
+// tools/pmc_summary.py read the three name tags from there, so those keep their values.
+enum : int {
+    P_SCHED = 1 << 18,      // production wave schedule: younger wave half at s_setprio 1 and one MFMA substep behind
+    P_SLAB = 1 << 20,       // wave-private epilogue slabs in LDS of their own, no epilogue barrier (even K-step counts)
+    P_X3IMG = 1 << 22,      // GELU output written as the three-part fp16x3 image [hi | hi/64 | lo*64]
+    P_TAG_OPROJ = 1 << 16,  // name tag (65536): the O-projection launches
+    P_TAG_FFN2 = 1 << 17,   // name tag (131072): the BertOutput launches (and RS_GEMM_GROUP_M_FFN2)
+    X_GANG_XCD = 1 << 27,   // LayerNorm epilogue: gangs formed inside one XCD (RS_LNGANG=xcd, the default)
+    X_TAG_FFN2 = 1 << 26,   // name tag (67108864): the BertOutput launch of the LayerNorm epilogue (K > 1024)
+    // timing diagnostics of gemm_x3s_kernel (wrong results; RS_DIAG build only)
+    X_DIAG_NOSTAGE = 1,        // no K-loop staging
+    X_DIAG_NOSTORE = 2,        // no epilogue stores
+    X_DIAG_NOWAIT = 8,         // the DMA never waited for
+    X_DIAG_PANEL0 = 1 << 25,   // every tile stores onto row panel 0 (no HBM write burst)
+    X_DIAG_STAMP = 1 << 28,    // the stamp build (rs_debug_stamps)
+};
+
 // LDS tile rows are BK fp16 = 2*BK bytes (BK = 64: 128 B, 8 chunks; BK = 32: 64 B, 4 chunks).
 // Chunk swizzle spreading the 16 rows a ds_read_b128 lane group reads over the 16 slots of
 // a 256-byte bank row: BK 64 -> chunk ^ ((row>>1)&7), BK 32 -> chunk ^ ((row>>2)&3).
@@ -60,11 +80,12 @@ __device__ __forceinline__ typename AccT<MS>::type mfma_f16(half8 a, half8 b, ty
 template <int MS>
 __device__ __forceinline__ int qcol(int g, int lane) { return MS == 32 ? 8 * g + 4 * (lane >> 5) : 4 * (lane >> 4); }
 
-// VAR bits: 128 (K loop software-pipelined by sched_group_barrier), 64 (non-temporal epilogue
-// stores), 8192 (v_mfma_f32_16x16x32_f16).  (The measured-slower alternatives of rounds 1-3 —
-// front-loaded reads, the direct permlane epilogue, the ping-pong wave rows, the two-buffer
-// cross-step pipeline — are recorded in profiles/r1_*; their code was removed in round 4.)
-template <int BM, int BN, int WM, int WN, int NSTAGE, int BK, int EPI, int VAR = 0>
+// The pipelined kernel: the K loop is software-pipelined by sched_group_barrier; the MFMA shape
+// and the store policy follow from the epilogue (MS, NT below).  (The measured-slower
+// alternatives of rounds 1-3 — front-loaded reads, the direct permlane epilogue, the ping-pong
+// wave rows, the two-buffer cross-step pipeline — are recorded in profiles/r1_*; their code was
+// removed in round 4; the unscheduled K loop, which no launch selected, went after round 6.)
+template <int BM, int BN, int WM, int WN, int NSTAGE, int BK, int EPI>
 __global__ void __launch_bounds__(WM * WN * 64)
 gemm_f16_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int n_tiles_n,
                 EpiArgs ep) {
@@ -72,7 +93,11 @@ gemm_f16_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
     constexpr int A_BYTES = BM * BK * 2;
     constexpr int STAGE = (BM + BN) * BK * 2;
     constexpr int WTM = BM / WM, WTN = BN / WN;
-    constexpr int MS = (VAR & 8192) ? 16 : 32;         // MFMA shape (VAR bit 8192: 16x16x32)
+    // MFMA shape: 16x16x32 everywhere except the logsumexp epilogue, whose in-register row
+    // reductions are written for the 32x32x16 accumulator layout
+    constexpr int MS = EPI == EPI_LSE ? 32 : 16;
+    // non-temporal epilogue stores (st16) for the fp16 outputs only
+    constexpr bool NT = EPI == EPI_BIAS_F16 || EPI == EPI_GELU_F16;
     constexpr int KPS = 512 / MS, CPS = KPS / 8, NQ = MS * MS / 256;
     typedef typename AccT<MS>::type accT;
     constexpr int TM = WTM / MS, TN = WTN / MS;
@@ -212,7 +237,7 @@ gemm_f16_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
         int nb = buf + NSTAGE - 1;
         if (nb >= NSTAGE) nb -= NSTAGE;
         if (kt + NSTAGE - 1 < nk) stage(nb, (kt + NSTAGE - 1) * BK);
-        if constexpr (VAR & 128) __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_sched_barrier(0);
         constexpr int NSUB = BK / KPS;         // k-substeps per stage
         const char* sA = smem + buf * STAGE;
         const char* sB = sA + A_BYTES;
@@ -249,24 +274,22 @@ gemm_f16_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
             mfmas(af0, bf0);
         }
         mfmas(af1, bf1);
-        if constexpr ((VAR & 128) != 0) {
-            // Software pipeline the scheduler will not find by itself (it serialises the
-            // fragment reads and the MFMAs that consume them, exposing LDS latency per
-            // substep): substep 0's reads, then substep s+1's reads one per MFMA of substep s.
-            constexpr int NR = TM + TN, NM = TM * TN;
-            static_assert(NM >= NR, "one read per MFMA slot");
-            __builtin_amdgcn_sched_group_barrier(0x100, NR, 0);
+        // Software pipeline the scheduler will not find by itself (it serialises the fragment
+        // reads and the MFMAs that consume them, exposing LDS latency per substep): substep
+        // 0's reads, then substep s+1's reads one per MFMA of substep s.
+        constexpr int NR = TM + TN, NM = TM * TN;
+        static_assert(NM >= NR, "one read per MFMA slot");
+        __builtin_amdgcn_sched_group_barrier(0x100, NR, 0);
 #pragma unroll
-            for (int s = 0; s < NSUB - 1; ++s) {
+        for (int s = 0; s < NSUB - 1; ++s) {
 #pragma unroll
-                for (int r = 0; r < NR; ++r) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                }
-                __builtin_amdgcn_sched_group_barrier(0x008, NM - NR, 0);
+            for (int r = 0; r < NR; ++r) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
             }
-            __builtin_amdgcn_sched_group_barrier(0x008, NM, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, NM - NR, 0);
         }
+        __builtin_amdgcn_sched_group_barrier(0x008, NM, 0);
         buf = buf + 1 == NSTAGE ? 0 : buf + 1;
     }
     // ---------------- epilogue.  acc[i][j][4g + e] = C[row][col + e],
@@ -352,7 +375,7 @@ gemm_f16_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
                         half8 h;
 #pragma unroll
                         for (int e = 0; e < 8; ++e) h[e] = (f16)x[e];
-                        st16<VAR>((uint4*)((f16*)ep.out + o), __builtin_bit_cast(uint4, h));
+                        st16<NT>((uint4*)((f16*)ep.out + o), __builtin_bit_cast(uint4, h));
                     } else if constexpr (EPI == EPI_GELU_F16) {
                         f16* orow = (f16*)ep.out + (size_t)row * ep.ldc;
                         half8 h, l, md;
@@ -362,14 +385,14 @@ gemm_f16_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
                             l[e] = x3_lo(x[e], h[e]);
                             md[e] = x3_mid(h[e]);
                         }
-                        st16<VAR>((uint4*)(orow + col), __builtin_bit_cast(uint4, h));
+                        st16<NT>((uint4*)(orow + col), __builtin_bit_cast(uint4, h));
                         if (ep.kx == 3) {
-                            st16<VAR>((uint4*)(orow + ep.nlog + col), __builtin_bit_cast(uint4, md));
-                            st16<VAR>((uint4*)(orow + 2 * ep.nlog + col), __builtin_bit_cast(uint4, l));
+                            st16<NT>((uint4*)(orow + ep.nlog + col), __builtin_bit_cast(uint4, md));
+                            st16<NT>((uint4*)(orow + 2 * ep.nlog + col), __builtin_bit_cast(uint4, l));
                         }
                     } else {  // fp32 outputs (residual already in acc)
-                        st16<VAR>((uint4*)((float*)ep.out + o), __builtin_bit_cast(uint4, make_float4(x[0], x[1], x[2], x[3])));
-                        st16<VAR>((uint4*)((float*)ep.out + o + 4), __builtin_bit_cast(uint4, make_float4(x[4], x[5], x[6], x[7])));
+                        st16<NT>((uint4*)((float*)ep.out + o), __builtin_bit_cast(uint4, make_float4(x[0], x[1], x[2], x[3])));
+                        st16<NT>((uint4*)((float*)ep.out + o + 4), __builtin_bit_cast(uint4, make_float4(x[4], x[5], x[6], x[7])));
                     }
                 }
             }
@@ -390,7 +413,9 @@ gemm_f16_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
 // rows < M_pad are all allocated, so NSTORE is exact).  The bias loads are inline asm so the
 // compiler's own (loop-merged, conservative) wait does not drain the stores; the wait asm
 // takes the bias registers as operands, so nothing reads them before it.
-template <int EPI, int VAR>
+// OPT: P_SCHED (the production wave schedule; without it the plain barrier-synchronised schedule,
+// which the tests keep as its bitwise reference), P_SLAB, P_X3IMG and the P_TAG_* name tags.
+template <int EPI, int OPT>
 __global__ void __launch_bounds__(512)
 gemm_persist_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int n_tiles_n,
                     int n_tiles, EpiArgs ep) {
@@ -406,9 +431,10 @@ gemm_persist_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K,
     constexpr int NSTORE = (WTM / 32) * 4;        // 16-B stores per wave per tile
     constexpr int NSUB = BK / KPS, NR = TM + TN, NM = TM * TN;
     static_assert(EPI == EPI_BIAS_F16 || EPI == EPI_GELU_F16, "fp16-output epilogues only");
-    // VAR 4194304: fp16x3 precision mode (kx = 3) — the GELU output is written as the
+    // P_X3IMG: fp16x3 precision mode (kx = 3) — the GELU output is written as the
     // three-part operand image [hi | hi/64 | lo·64] of the next GEMM (ep.nlog columns apart)
-    constexpr bool X3 = (VAR & 4194304) != 0;
+    constexpr bool X3 = (OPT & P_X3IMG) != 0;
+    constexpr bool SLAB = (OPT & P_SLAB) != 0;
     static_assert(!X3 || EPI == EPI_GELU_F16, "x3 image: GELU");
     static_assert(NW * 32 * 128 <= STAGE, "epilogue slab fits in one buffer");
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -421,9 +447,9 @@ gemm_persist_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K,
 
     int t = blockIdx.x;
     if (t >= n_tiles) return;
-    // VAR 262144: static priority for the second-dispatched wave half (MI355X_MICROARCH
+    // P_SCHED: static priority for the second-dispatched wave half (MI355X_MICROARCH
     // 'Two waves per SIMD' item 4: the younger wave of each SIMD loses every arbitration)
-    if constexpr ((VAR & 262144) != 0) {
+    if constexpr ((OPT & P_SCHED) != 0) {
         if (wave >= NW / 2) __builtin_amdgcn_s_setprio(1);
     }
     auto tile_of = [&](int tt, int& m0, int& n0) {
@@ -506,7 +532,7 @@ gemm_persist_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K,
                     acc[i][j][4 * g + 3] = bz[j * NQ + g].w;
                 }
         // ---- K loop: stage kt landed (this tile's stage 0 was waited with the bias).  STAG:
-        // this wave runs the staggered schedule (VAR 524288, younger half); one loop body per
+        // this wave runs the staggered schedule (P_SCHED, younger half); one loop body per
         // schedule, chosen once per tile, so each is register-allocated on its own.
         auto kloop = [&](auto stag_tag) {
         constexpr bool STAG = decltype(stag_tag)::value;
@@ -603,17 +629,17 @@ gemm_persist_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K,
             __builtin_amdgcn_sched_group_barrier(0x008, NM, 0);
         }
         };
-        if constexpr (NSUB == 4 && (VAR & 524288) != 0) {
+        if constexpr (NSUB == 4 && (OPT & P_SCHED) != 0) {
             if (wave >= NW / 2) kloop(std::true_type{});
             else kloop(std::false_type{});
         } else {
             kloop(std::false_type{});
         }
         // ---- transition: next tile's stage 0 + bias, then this tile's epilogue
-        // every wave is done reading the ring (the slab lives in buffer 1).  VAR 1048576: the
+        // every wave is done reading the ring (the slab lives in buffer 1).  P_SLAB: the
         // slabs have their own LDS, and with an even K-step count the next tile's stage 0
         // (buffer 0) was last read before the final K-step's barrier, so no wave waits here
-        if (!(VAR & 1048576) || (nk & 1)) asm volatile("s_barrier" ::: "memory");
+        if (!SLAB || (nk & 1)) asm volatile("s_barrier" ::: "memory");
         const int cm0 = m0, cn0 = n0;
         bool more = false;
         auto issue_next = [&]() {
@@ -638,7 +664,7 @@ gemm_persist_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K,
             // the 8-lane write groups (8 rows, one chunk) and the 16-lane read groups (two rows,
             // all chunks) are both conflict-free (a padded layout measured 2-way on both, round 1)
             static_assert(WTN == 64, "slab rows of 8 chunks");
-            char* slb = smem + ((VAR & 1048576) ? 2 * STAGE : STAGE) + wave * 32 * 128;
+            char* slb = smem + (SLAB ? 2 * STAGE : STAGE) + wave * 32 * 128;
             if constexpr (X3) {
                 // fp16x3 image [hi | hi/64 | lo·64] (common.h put_split): GELU once, in place
 #pragma unroll
@@ -698,7 +724,7 @@ gemm_persist_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K,
                 if constexpr (STORE_NOW) {
 #pragma unroll
                     for (int it = 0; it < 4; ++it)
-                        st16<64>((uint4*)(obase + img * ep.nlog + (size_t)(i32 * 32 + it * 8) * ep.ldc), ov[0][it]);
+                        st16<true>((uint4*)(obase + img * ep.nlog + (size_t)(i32 * 32 + it * 8) * ep.ldc), ov[0][it]);
                 }
             }
             };
@@ -721,7 +747,7 @@ gemm_persist_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K,
         for (int i = 0; i < WTM / 32; ++i)
 #pragma unroll
             for (int it = 0; it < 4; ++it)
-                st16<64>((uint4*)(obase + (size_t)(i * 32 + it * 8) * ep.ldc), ov[i][it]);
+                st16<true>((uint4*)(obase + (size_t)(i * 32 + it * 8) * ep.ldc), ov[i][it]);
         if (!more) break;
         RS_PERSIST_WAIT(16);
         static_assert(NSTORE == 16, "RS_PERSIST_WAIT count");
@@ -945,7 +971,11 @@ __device__ __forceinline__ void lnr_done(const EpiArgs& ep, int lane) {
     for (int i = 0; i < 3; ++i) __hip_atomic_store((lgu32*)(c + w[i]), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <int EPI, int VAR>
+// OPT: for the LayerNorm epilogue the gang form (X_GANG_XCD) and the BertOutput name tag
+// (X_TAG_FFN2); in the RS_DIAG build also the X_DIAG_* timing diagnostics.  Everything else the
+// LayerNorm build does differently (LNR below: permuted output columns, the residual by LDS-DMA,
+// the next tile's stage 0 after the row statistics) comes with the epilogue, not with an option.
+template <int EPI, int OPT>
 __global__ void __launch_bounds__(512)
 gemm_x3s_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int ldw, int n_tiles_n, int n_tiles,
                 EpiArgs ep) {
@@ -957,14 +987,13 @@ gemm_x3s_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
     static_assert(EPI == EPI_BIAS_F32 || EPI == EPI_GELU_F16 || EPI == EPI_LNRES_IMG, "x3s epilogues");
     constexpr bool LNR = EPI == EPI_LNRES_IMG;
     // Timing diagnostics (wrong results; compiled only into the RS_DIAG build, librescore_diag.so,
-    // never into the shipped library): DV 1 no K-loop staging, 2 no epilogue stores, 8 the DMA
-    // never waited for, 33554432 every tile stores onto row panel 0 (no HBM write burst),
-    // 268435456 the stamp build (rs_debug_stamps): s_memtime at the tile's phase boundaries,
-    // per-phase cycle sums in scalar registers, stored by thread 0 into
-    // ep.dbg[blockIdx.x * 16 + phase] (a buffer of its own: no output depends on it)
-    constexpr int DV = RS_DIAG ? VAR & (1 | 2 | 8 | 33554432 | 268435456) : 0;
-    static_assert(!LNR || (DV & 2) == 0, "the LayerNorm epilogue has no no-store diagnostic");
-    constexpr bool STAMP = (DV & 268435456) != 0;
+    // never into the shipped library): the X_DIAG_* options.  X_DIAG_STAMP, the stamp build
+    // (rs_debug_stamps): s_memtime at the tile's phase boundaries, per-phase cycle sums in scalar
+    // registers, stored by thread 0 into ep.dbg[blockIdx.x * 16 + phase] (a buffer of its own: no
+    // output depends on it)
+    constexpr int DV = RS_DIAG ? OPT & (X_DIAG_NOSTAGE | X_DIAG_NOSTORE | X_DIAG_NOWAIT | X_DIAG_PANEL0 | X_DIAG_STAMP) : 0;
+    static_assert(!LNR || (DV & X_DIAG_NOSTORE) == 0, "the LayerNorm epilogue has no no-store diagnostic");
+    constexpr bool STAMP = (DV & X_DIAG_STAMP) != 0;
     unsigned long long st_sum[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_prev = 0;
     auto stamp = [&](int ph) __attribute__((always_inline)) {
         if constexpr (STAMP) {
@@ -977,7 +1006,6 @@ gemm_x3s_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
         }
     };
     stamp(-1);
-    static_assert((VAR & 16777216) == 0 || LNR, "the permuted-column layout is written for the LayerNorm epilogue");
     extern __shared__ __attribute__((aligned(16))) char smem[];        // the LDS-DMA ring (2 stages)
     // wave-private epilogue slabs: a separate LDS object, so the compiler can tell the slab
     // reads do not alias the LDS-DMA writes in flight (no vmcnt wait before them)
@@ -997,7 +1025,7 @@ gemm_x3s_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
         // walks panel list l (panels l, l + G / ntn, ...; member m keeps column tile m: first tile
         // l * ntn + m, then t += gridDim.x), then the next untaken list.  lnr_gang_ticket (thread 0)
         // returns l * ntn + m.
-        if (tid == 0) *(unsigned*)(slabs + 2048) = lnr_gang_ticket<(VAR & 134217728) != 0>(ep, n_tiles_n, n_tiles / n_tiles_n);
+        if (tid == 0) *(unsigned*)(slabs + 2048) = lnr_gang_ticket<(OPT & X_GANG_XCD) != 0>(ep, n_tiles_n, n_tiles / n_tiles_n);
         __syncthreads();
         t = (int)*(const unsigned*)(slabs + 2048);
     }
@@ -1008,7 +1036,6 @@ gemm_x3s_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
         }
         return;
     }
-    if ((unsigned)t >= (unsigned)n_tiles) return;
     // the younger wave half (waves 4-7, one per SIMD beside an older partner) at s_setprio 1
     // (MI355X_MICROARCH 'Two waves per SIMD' item 4)
     if (wave >= NW / 2) __builtin_amdgcn_s_setprio(1);
@@ -1039,14 +1066,15 @@ gemm_x3s_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
     const size_t ld2 = (size_t)2 * K;
     __amdgpu_buffer_rsrc_t rsA, rsW;
     int voffA[4], voffW[4];                       // lane byte offsets: (p & 1) row half x 8-row half
-    // VAR 16777216: output columns permuted inside each 32-column group so that a lane's two
+    // LayerNorm build: output columns permuted inside each 32-column group so that a lane's two
     // 16-column MFMA blocks 2m, 2m + 1 hold 8 CONSECUTIVE output columns (32 m + 8 q4 .. + 7)
     // instead of two runs of 4: W image row 32 m + 16 jj + 4 q + e is W row 32 m + 8 q + 4 jj + e.
-    // The epilogue's per-lane loads (bias, residual image, LayerNorm weights) become 16-B loads.
-    constexpr bool PERM = (VAR & 16777216) != 0;
-    constexpr bool RESDMA = LNR && (VAR & 4) != 0;     // the LayerNorm epilogue's residual by LDS-DMA
+    // The epilogue's per-lane loads (bias, LayerNorm weights) become 16-B loads and the residual
+    // image's lines land in the accumulator layout (+1.1 % end to end, profiles/r3p2_lnperm_ab.txt).
+    // (The LayerNorm build with unpermuted columns — 8-B loads, twice as many — was removed with
+    // its option bit; the fp32 and GELU builds keep the unpermuted formulas, the `: ...` arms.)
     auto wperm = [](int L) {
-        return PERM ? (L & ~31) | (((L >> 2) & 3) << 3) | (((L >> 4) & 1) << 2) | (L & 3) : L;
+        return LNR ? (L & ~31) | (((L >> 2) & 3) << 3) | (((L >> 4) & 1) << 2) | (L & 3) : L;
     };
 #pragma unroll
     for (int h = 0; h < 2; ++h)
@@ -1062,7 +1090,7 @@ gemm_x3s_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
         rsW = __builtin_amdgcn_make_buffer_rsrc((void*)(W + (size_t)n0 * ldw), (short)0, 256 * ldw * 2, 0x00020000);
     };
     auto piece = [&](int buf, int k0, int p) {
-        if constexpr ((DV & 1) != 0) return;      // diagnostic: no K-loop staging (stale tiles)
+        if constexpr ((DV & X_DIAG_NOSTAGE) != 0) return;      // diagnostic: no K-loop staging (stale tiles)
         const int r = p >> 1;
         const int dofs = (r >> 1) * 2 * REG + ((p & 1) * 128 + wave * 16 + 8 * (r & 1)) * 128;
         auto* dst = (__attribute__((address_space(3))) void*)(smem + buf * STAGE + dofs);
@@ -1163,7 +1191,7 @@ gemm_x3s_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
             for (int j = 0; j < 4; ++j) acc16[i][j] = (f32x4)(0.f);
         // step kt landed for this wave (at a tile's first step the previous tile's stores are
         // younger and stay in flight); the barrier: landed for every wave, and every wave is done
-        // reading step kt-1's buffer, which now receives step kt+1.  (DV 8, diagnostic: the DMA is
+        // reading step kt-1's buffer, which now receives step kt+1.  (X_DIAG_NOWAIT: the DMA is
         // never waited for — isolates its latency from its presence.)
         int kt0 = 0;
         if constexpr (LNR) {
@@ -1171,7 +1199,7 @@ gemm_x3s_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
             // compiler, the peeled step tested a hoisted loop-invariant flag that this build spilled,
             // and the reload's vmcnt(0) drained the previous tile's 32 epilogue stores at every tile
             // start (the fp32 / GELU builds keep the loop: peeled by hand they spill)
-            if constexpr ((DV & 8) == 0) {
+            if constexpr ((DV & X_DIAG_NOWAIT) == 0) {
                 if (!first) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NSTORE) : "memory");
                 else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
@@ -1184,7 +1212,7 @@ gemm_x3s_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
         }
         for (int kt = kt0; kt < nk; ++kt) {
             const int cur = (par + kt) & 1;
-            if constexpr ((DV & 8) != 0) {
+            if constexpr ((DV & X_DIAG_NOWAIT) != 0) {
             } else if (kt == 0 && !first) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NSTORE) : "memory");
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             asm volatile("s_barrier" ::: "memory");
@@ -1203,7 +1231,7 @@ gemm_x3s_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
         // the wave's 64): only the bias loads (and, LayerNorm build, the residual's first pieces)
         // are outstanding here (the last K-step issued no DMA), so one vmcnt(0) waits for exactly
         // them; inline asm keeps the compiler from placing its own wait
-        // LayerNorm build (VAR 4): the residual's first two row blocks go out as LDS-DMA before the
+        // LayerNorm build: the residual's first two row blocks go out as LDS-DMA before the
         // bias loads, so their latency and the bias loads' overlap (lnres_epilogue streams the rest)
         const int rbo = (last ^ 1) * STAGE + wave * 8192;
         const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc(
@@ -1222,14 +1250,14 @@ gemm_x3s_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rsR, dst, 16, voR[q], rb * 16 * ep.ldc * 2, 0, 0);
             }
         };
-        if constexpr (RESDMA) {
+        if constexpr (LNR) {
             issue(0);
             issue(1);
         }
         f32x4 bq[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float* bp = ep.bias + cn0 + wn * WTN + (PERM ? 32 * (j >> 1) + 8 * q4 + 4 * (j & 1) : 16 * j + 4 * q4);
+            const float* bp = ep.bias + cn0 + wn * WTN + (LNR ? 32 * (j >> 1) + 8 * q4 + 4 * (j & 1) : 16 * j + 4 * q4);
             asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(bq[j]) : "v"(bp) : "memory");
         }
         asm volatile("s_waitcnt vmcnt(0)" : "+v"(bq[0]), "+v"(bq[1]), "+v"(bq[2]), "+v"(bq[3]) : : "memory");
@@ -1242,16 +1270,17 @@ gemm_x3s_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
             if (t >= n_tiles && !lnr_next_list(ep, t, nlist, cm0 / BM, cn0 / BM, n_tiles_n, n_tiles, wave, lane)) break;
         }
         more = t < n_tiles;
-        // VAR 1073741824 (the LayerNorm build's default): the next tile's stage 0 issued after the
-        // row statistics instead (lnres_epilogue's caller) — its eight back-to-back DMA issues cost
-        // this phase ~6k cycles per tile here, where nothing hides them (the residual phase is
-        // unchanged either way; profiles/r5late0_stage0_after_stats.txt).  It still lands before the
-        // next tile's K-step 0, whose vmcnt(NSTORE) leaves only the younger epilogue stores in flight.
-        constexpr bool LATE0 = LNR && (VAR & 1073741824) != 0;
+        // LayerNorm build: the next tile's stage 0 is issued after the row statistics instead
+        // (lnres_epilogue's caller) — its eight back-to-back DMA issues cost this phase ~6k cycles
+        // per tile here, where nothing hides them (O-projection -1.1 %, BertOutput -0.7 %, the
+        // residual phase unchanged either way; profiles/r5late0_stage0_after_stats.txt).  It still
+        // lands before the next tile's K-step 0, whose vmcnt(NSTORE) leaves only the younger
+        // epilogue stores in flight.  (The LayerNorm build with the early stage 0 was removed with
+        // its option bit: the residual DMA below needs the buffer free until then.)
         if (more) {
             tile_of(t, m0, n0);
             set_rsrc(m0, n0);
-            if constexpr (!LATE0) stage(last ^ 1, 0);
+            if constexpr (!LNR) stage(last ^ 1, 0);
         }
         stamp(1);                                                 // bias wait + next tile's stage 0
         // bias (+ GELU) of row blocks [i0, i1)
@@ -1271,21 +1300,16 @@ gemm_x3s_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
                     }
         };
             auto lnres_epilogue = [&]() {
-                const int H = ep.nlog, ldc = ep.ldc, ntn = n_tiles_n;
+                const int H = ep.nlog, ntn = n_tiles_n;
                 const int panel = cm0 / BM, tcol = cn0 / BM;
                 const unsigned long long tag = (unsigned long long)ep.ln_tag << 32;
-                const f16* img = (const f16*)ep.out;
-                const int c0 = cn0 + wn * WTN + 4 * q4;
                 // x = (acc + bias) + h, the residual image h = hi + lo/64 read in the accumulator
-                // layout, four row blocks at a time (as ln_res_img forms it); the permuted-column
-                // layout (PERM) halves its load count: +1.1 % end to end.  (Reading it during the K
+                // layout (as ln_res_img forms it), one row block at a time.  (Reading it during the K
                 // loop instead, one row block per K-step added into the accumulators, measured
                 // neutral — 63,277 vs 63,263 masked fwd/s, profiles/r5b_lnkres_ab.txt — and made a
-                // row's sum depend on its position in the tile, so it was removed.)
-                // (two row blocks per batch: four would hold 64 registers of residual beside the 128
-                // accumulators, and the spills that forced reloaded values whose waits drained the
-                // next tile's stage 0 inside the statistics publish)
-                constexpr int RB2 = 2;
+                // row's sum depend on its position in the tile, so it was removed.  Reading it by
+                // per-lane global loads, two row blocks per batch, lost to the LDS-DMA below and was
+                // removed with its option bit.)
                 // per row block: acc <- acc / 64 + bias + (hi + lo/64) from packed (hi, lo) fp16 pairs
                 auto add_res = [&](int rb, const half4 (&rh)[4], const half4 (&rl)[4]) __attribute__((always_inline)) {
 #pragma unroll
@@ -1299,15 +1323,17 @@ gemm_x3s_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
                             acc16[rb][j][e] = __builtin_fmaf(acc16[rb][j][e], X3_DOWN, bq[j][e]) + hres[e];
                     }
                 };
-                if constexpr (RESDMA) {
-                    // VAR 4: the residual by whole-line LDS-DMA pieces (8 rows x 128 B, as the K loop
+                {
+                    // The residual by whole-line LDS-DMA pieces (8 rows x 128 B, as the K loop
                     // stages its operands) into this wave's 8 KiB of the NEXT tile's stage-0 buffer —
                     // free here: its last reads (K-step nk - 2) are behind the last K-step's barrier, and
-                    // LATE0 issues stage 0 into it only after the statistics.  Two row blocks in
+                    // stage 0 is issued into it only after the statistics.  Two row blocks in
                     // flight; the lane reads its (hi, lo) 16-B chunks back in the accumulator layout
-                    // (chunk c of LDS row n at c ^ ((n >> 1) & 7), as the K loop's images).
+                    // (chunk c of LDS row n at c ^ ((n >> 1) & 7), as the K loop's images; the
+                    // permuted columns make a lane's two blocks one 16-B chunk per part).
                     // (pieces of row blocks 0 and 1 issued at the transition, before the bias loads)
-                    static_assert(!RESDMA || (LATE0 && PERM), "the residual DMA needs the late stage 0");
+                    // Round 6: O-projection -1.9 %, BertOutput -1.0 %, C3 +0.4 %, bitwise against the
+                    // global-load form; profiles/r6o_lnres_residual_dma.txt.
                     const uint32_t lrow = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)smem + rbo +
                                           r16 * 128;
                     const uint32_t lh = lrow + ((q4 ^ ((r16 >> 1) & 7)) << 4), ll = lrow + (((q4 + 4) ^ ((r16 >> 1) & 7)) << 4);
@@ -1335,37 +1361,6 @@ gemm_x3s_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
                                              (half4){vl1[0], vl1[1], vl1[2], vl1[3]}, (half4){vl1[4], vl1[5], vl1[6], vl1[7]}};
                         add_res(rb, rh, rl);
                     }
-                }
-#pragma unroll
-                for (int hh = 0; hh < (RESDMA ? 0 : 8 / RB2); ++hh) {
-                    half4 rh0[RB2][4], rl0[RB2][4];
-#pragma unroll
-                    for (int ii = 0; ii < RB2; ++ii) {
-                        // the interleaved image row: column c's hi at il_hi(c), its lo 32 halves on
-                        const f16* prow_img = img + (size_t)(cm0 + wm * WTM + 16 * (RB2 * hh + ii) + r16) * ldc;
-                        if constexpr (PERM) {
-                            // blocks 2m, 2m + 1: 8 consecutive columns (32-column group m of the
-                            // wave's 64), one 16-B load per part
-#pragma unroll
-                            for (int m = 0; m < 2; ++m) {
-                                const f16* p = prow_img + 2 * (cn0 + wn * WTN) + 64 * m + 8 * q4;
-                                const half8 vh = *(const half8*)p, vl = *(const half8*)(p + 32);
-                                rh0[ii][2 * m] = (half4){vh[0], vh[1], vh[2], vh[3]};
-                                rh0[ii][2 * m + 1] = (half4){vh[4], vh[5], vh[6], vh[7]};
-                                rl0[ii][2 * m] = (half4){vl[0], vl[1], vl[2], vl[3]};
-                                rl0[ii][2 * m + 1] = (half4){vl[4], vl[5], vl[6], vl[7]};
-                            }
-                        } else {
-#pragma unroll
-                            for (int j = 0; j < 4; ++j) {
-                                const f16* p = prow_img + il_hi(c0 + 16 * j);
-                                rh0[ii][j] = *(const half4*)p;
-                                rl0[ii][j] = *(const half4*)(p + 32);
-                            }
-                        }
-                    }
-#pragma unroll
-                    for (int ii = 0; ii < RB2; ++ii) add_res(RB2 * hh + ii, rh0[ii], rl0[ii]);
                 }
                 stamp(2);                                         // residual read + add
                 // row partials over the wave's 64 columns (lanes l, l^16, l^32, l^48 share a row),
@@ -1501,7 +1496,7 @@ gemm_x3s_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
                 f32x4 gq[4], bb[4];                      // LayerNorm weight / bias of the lane's columns
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const int cj = PERM ? cn0 + wn * WTN + 32 * (j >> 1) + 8 * q4 + 4 * (j & 1) : c0 + 16 * j;
+                    const int cj = cn0 + wn * WTN + 32 * (j >> 1) + 8 * q4 + 4 * (j & 1);   // permuted columns
                     gq[j] = *(const f32x4*)(ep.res_g + cj);
                     bb[j] = *(const f32x4*)(ep.res_b + cj);
                 }
@@ -1518,17 +1513,15 @@ gemm_x3s_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
             };
             // the GELU image: each row-block pair's bias + GELU right before its slab pass, so that
             // VALU work overlaps the previous pair's LDS and global stores
-            constexpr bool LATE = EPI == EPI_GELU_F16 && (DV & 2) == 0;
+            constexpr bool LATE = EPI == EPI_GELU_F16 && (DV & X_DIAG_NOSTORE) == 0;
             if constexpr (LNR) {
                 if (lnres_epilogue()) {
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the next tile's stage 0 landed
                     break;
                 }
-                if constexpr (LATE0) {
-                    if (more) stage(last ^ 1, 0);
-                }
+                if (more) stage(last ^ 1, 0);    // the late stage 0 (see the transition above)
             } else if constexpr (!LATE) finish(0, 8);
-            if constexpr ((DV & 2) != 0) {       // diagnostic: no epilogue stores (acc kept alive)
+            if constexpr ((DV & X_DIAG_NOSTORE) != 0) {       // diagnostic: no epilogue stores (acc kept alive)
 #pragma unroll
                 for (int i = 0; i < 8; ++i)
 #pragma unroll
@@ -1544,8 +1537,8 @@ gemm_x3s_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
             int lns = lane;
             if constexpr (LNR) asm volatile("" : "+v"(lns));
             const int rr0 = lns >> 3, c16 = lns & 7;
-            // DV 33554432 (diagnostic): every tile stores onto the rows of row panel 0
-            const int sm0 = (DV & 33554432) ? 0 : cm0;
+            // X_DIAG_PANEL0 (diagnostic): every tile stores onto the rows of row panel 0
+            const int sm0 = (DV & X_DIAG_PANEL0) ? 0 : cm0;
             if constexpr (EPI == EPI_BIAS_F32) {
                 // 32 x 32 fp32 slab blocks: row blocks 2 i2 + a, column blocks 2 j2 + b
 #pragma unroll
@@ -1563,7 +1556,7 @@ gemm_x3s_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
                         uint4 v[4];
                         slab_read4(slb, rr0, c16, v);
 #pragma unroll
-                        for (int it = 0; it < 4; ++it) st16<64>((uint4*)(ob + (size_t)(it * 8 + rr0) * ep.ldc), v[it]);
+                        for (int it = 0; it < 4; ++it) st16<true>((uint4*)(ob + (size_t)(it * 8 + rr0) * ep.ldc), v[it]);
                     }
             } else {
                 // the interleaved two-part image in 32 x 64 slab blocks: row blocks 2 i2 + a, one
@@ -1588,7 +1581,7 @@ gemm_x3s_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
                                 const f32x2 s01 = (f32x2){xv[0], xv[1]} * X3_UP, s23 = (f32x2){xv[2], xv[3]} * X3_UP;
                                 hl = __builtin_bit_cast(half4, (uint2){mix_lo2(hv.x, s01.x, s01.y, -X3_UP),
                                                                        mix_lo2(hv.y, s23.x, s23.y, -X3_UP)});
-                                const int row = 16 * a + r16, byte = PERM ? 16 * q4 + 8 * jj : 32 * jj + 8 * q4;
+                                const int row = 16 * a + r16, byte = LNR ? 16 * q4 + 8 * jj : 32 * jj + 8 * q4;
                                 *(half4*)(slb + row * 128 + (((byte >> 4) ^ (row & 7)) << 4) + (byte & 8)) = hh;
                                 *(half4*)(slb + row * 128 + ((((byte >> 4) + 4) ^ (row & 7)) << 4) + (byte & 8)) = hl;
                             }
@@ -1596,7 +1589,7 @@ gemm_x3s_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
                         uint4 v[4];
                         slab_read4(slb, rr0, c16, v);
 #pragma unroll
-                        for (int it = 0; it < 4; ++it) st16<64>((uint4*)(ob + (size_t)(it * 8 + rr0) * ep.ldc), v[it]);
+                        for (int it = 0; it < 4; ++it) st16<true>((uint4*)(ob + (size_t)(it * 8 + rr0) * ep.ldc), v[it]);
                     }
                 }
             }
@@ -1647,13 +1640,13 @@ hipError_t smem_attr_once(const void* fn, int smem, std::atomic<unsigned>& devs)
     return hipSuccess;
 }
 
-template <int EPI, int VAR = 0>
+template <int EPI, int OPT = 0>
 hipError_t launch_x3s(const f16* A, const f16* W, int M_pad, int N_pad, int K, const EpiArgs& ep, hipStream_t st,
                       int ldw = 0) {
     constexpr int smem = 2 * 65536;                  // ring (2 x 64 KiB); + 32 KiB static wave slabs
     if (K % 32 || K < 64 || M_pad % 256 || N_pad % 256) return hipErrorInvalidValue;
     static std::atomic<unsigned> attr_devs{0};      // devices whose LDS limit is raised
-    if (hipError_t e = smem_attr_once((const void*)gemm_x3s_kernel<EPI, VAR>, smem, attr_devs)) return e;
+    if (hipError_t e = smem_attr_once((const void*)gemm_x3s_kernel<EPI, OPT>, smem, attr_devs)) return e;
     const int ntn = N_pad / 256, n_tiles = (M_pad / 256) * ntn;
     const int cus = n_cus() / 8 * 8;
     int grid = n_tiles <= cus ? n_tiles : cus;
@@ -1677,53 +1670,53 @@ hipError_t launch_x3s(const f16* A, const f16* W, int M_pad, int N_pad, int K, c
         e2.ln_tag = ln_tag_next();
     }
     const int ldw2 = ldw > 0 ? ldw : 2 * K;
-    hipLaunchKernelGGL((gemm_x3s_kernel<EPI, VAR>), dim3(grid), dim3(512), smem, st, A, W, K, ldw2, ntn, n_tiles, e2);
+    hipLaunchKernelGGL((gemm_x3s_kernel<EPI, OPT>), dim3(grid), dim3(512), smem, st, A, W, K, ldw2, ntn, n_tiles, e2);
     return hipGetLastError();
 }
 
-template <int EPI, int VAR = 0>
+template <int EPI, int OPT = 0>
 hipError_t launch_persist(const f16* A, const f16* W, int M_pad, int N_pad, int K, const EpiArgs& ep,
                           hipStream_t st) {
-    // VAR 1048576: wave-private epilogue slabs in their own 32 KiB after the ring (160 KiB)
-    constexpr int smem = 2 * 512 * 64 * 2 + ((VAR & 1048576) ? 8 * 32 * 128 : 0);
+    // P_SLAB: wave-private epilogue slabs in their own 32 KiB after the ring (160 KiB)
+    constexpr int smem = 2 * 512 * 64 * 2 + ((OPT & P_SLAB) ? 8 * 32 * 128 : 0);
     if (K % 64 || M_pad % 256 || N_pad % 256) return hipErrorInvalidValue;
     static std::atomic<unsigned> attr_devs{0};      // devices whose LDS limit is raised
-    if (hipError_t e = smem_attr_once((const void*)gemm_persist_kernel<EPI, VAR>, smem, attr_devs)) return e;
+    if (hipError_t e = smem_attr_once((const void*)gemm_persist_kernel<EPI, OPT>, smem, attr_devs)) return e;
     const int ntn = N_pad / 256, n_tiles = (M_pad / 256) * ntn;
     const int cus = n_cus() / 8 * 8;
     const int grid = n_tiles <= cus ? n_tiles : cus;
     // 8 row panels per group (QKV -3 % vs 4, end to end; profiles/r1_ab_session2.txt)
     static const int gm_env = getenv("RS_GEMM_GROUP_M_P") ? atoi(getenv("RS_GEMM_GROUP_M_P")) : 0;
-    // BertOutput (VAR tag 131072, K = 3072): RS_GEMM_GROUP_M_FFN2 row panels per group
+    // BertOutput (P_TAG_FFN2, K = 3072): RS_GEMM_GROUP_M_FFN2 row panels per group
     static const int gm_ffn2 = getenv("RS_GEMM_GROUP_M_FFN2") ? atoi(getenv("RS_GEMM_GROUP_M_FFN2")) : 0;
     EpiArgs e2 = ep;
-    e2.group_m = (VAR & 131072) && gm_ffn2 > 0 ? gm_ffn2 : gm_env > 0 ? gm_env : 8;
-    hipLaunchKernelGGL((gemm_persist_kernel<EPI, VAR>), dim3(grid), dim3(512), smem, st, A, W, K, ntn, n_tiles, e2);
+    e2.group_m = (OPT & P_TAG_FFN2) && gm_ffn2 > 0 ? gm_ffn2 : gm_env > 0 ? gm_env : 8;
+    hipLaunchKernelGGL((gemm_persist_kernel<EPI, OPT>), dim3(grid), dim3(512), smem, st, A, W, K, ntn, n_tiles, e2);
     return hipGetLastError();
 }
 
-// name tags (kernel names only): 1 = O projection (VAR 65536), 2 = BertOutput (VAR 131072)
+// name tags (kernel names only): 1 = O projection (P_TAG_OPROJ), 2 = BertOutput (P_TAG_FFN2)
 template <int EPI, int V>
 hipError_t persist_tagged(int tag, const f16* A, const f16* W, int M_pad, int N_pad, int K, const EpiArgs& ep,
                           hipStream_t st) {
-    return tag == 1 ? launch_persist<EPI, V | 65536>(A, W, M_pad, N_pad, K, ep, st)
-         : tag == 2 ? launch_persist<EPI, V | 131072>(A, W, M_pad, N_pad, K, ep, st)
+    return tag == 1 ? launch_persist<EPI, V | P_TAG_OPROJ>(A, W, M_pad, N_pad, K, ep, st)
+         : tag == 2 ? launch_persist<EPI, V | P_TAG_FFN2>(A, W, M_pad, N_pad, K, ep, st)
                     : launch_persist<EPI, V>(A, W, M_pad, N_pad, K, ep, st);
 }
 
-template <int BM, int BN, int WM, int WN, int NSTAGE, int BK, int EPI, int VAR = 0>
+template <int BM, int BN, int WM, int WN, int NSTAGE, int BK, int EPI>
 hipError_t launch_t(const f16* A, const f16* W, int M_pad, int N_pad, int K, const EpiArgs& ep,
                     hipStream_t st) {
     constexpr int smem = NSTAGE * (BM + BN) * BK * 2;
     if (K % BK) return hipErrorInvalidValue;
     static std::atomic<unsigned> attr_devs{0};      // devices whose LDS limit is raised
-    if (hipError_t e = smem_attr_once((const void*)gemm_f16_kernel<BM, BN, WM, WN, NSTAGE, BK, EPI, VAR>, smem, attr_devs)) return e;
+    if (hipError_t e = smem_attr_once((const void*)gemm_f16_kernel<BM, BN, WM, WN, NSTAGE, BK, EPI>, smem, attr_devs)) return e;
     const int ntn = N_pad / BN;
     const int grid = (M_pad / BM) * ntn;
     static const int gm_env = getenv("RS_GEMM_GROUP_M") ? atoi(getenv("RS_GEMM_GROUP_M")) : 0;
     EpiArgs e2 = ep;
     e2.group_m = gm_env > 0 ? gm_env : 4;   // 4 row panels per group (measured best of 1/2/4/8/16)
-    hipLaunchKernelGGL((gemm_f16_kernel<BM, BN, WM, WN, NSTAGE, BK, EPI, VAR>), dim3(grid), dim3(WM * WN * 64),
+    hipLaunchKernelGGL((gemm_f16_kernel<BM, BN, WM, WN, NSTAGE, BK, EPI>), dim3(grid), dim3(WM * WN * 64),
                        smem, st, A, W, K, ntn, e2);
     return hipGetLastError();
 }
@@ -1731,12 +1724,12 @@ hipError_t launch_t(const f16* A, const f16* W, int M_pad, int N_pad, int K, con
 // fp16-operand GEMMs (the fp16 precision mode, the K-concatenated fp16x3 form RS_X3S=0, the
 // last layer's query rows and the MLM head), the measured-best variant per epilogue:
 //   * bias / GELU fp16 outputs (kx = 1): the persistent kernel, younger wave half at s_setprio 1
-//     and one MFMA substep behind, wave-private epilogue slabs without the epilogue barrier for
-//     the bias epilogue (VAR 786432 | 1048576; +1.2 / +1.5 / +1.6-1.9 %, profiles/r1_session3_probes.txt);
-//   * the GELU three-part image of the K-concatenated fp16x3 form: the persistent kernel (VAR 4194304);
+//     and one MFMA substep behind (P_SCHED), wave-private epilogue slabs without the epilogue
+//     barrier for the bias epilogue (P_SLAB; +1.2 / +1.5 / +1.6-1.9 %, profiles/r1_session3_probes.txt);
+//   * the GELU three-part image of the K-concatenated fp16x3 form: the persistent kernel (P_X3IMG);
 //   * everything else (fp32 outputs, the residual epilogues, the decoder logsumexp): the pipelined
 //     256 x 256 (N % 256 == 0) or 256 x 128 kernel, 16x16x32 MFMA except the logsumexp epilogue
-//     (32x32x16), non-temporal stores for fp16 outputs (VAR 64).
+//     (32x32x16), non-temporal stores for fp16 outputs (both decided inside gemm_f16_kernel).
 // Measured-slower alternatives (tile configurations 2-7, 32x32x16 in the pipelined kernel, the
 // unstaggered persistent schedules, direct residual stores, ...) are recorded in profiles/r1_*;
 // their code paths were removed in round 4.
@@ -1745,22 +1738,16 @@ hipError_t launch_epi(const f16* A, const f16* W, int M_pad, int N_pad, int K, c
                       hipStream_t st, int tag) {
     const bool n256 = N_pad % 256 == 0;
     if constexpr (EPI == EPI_GELU_F16) {
-        if (n256 && ep.kx == 3) return launch_persist<EPI, 786432 | 4194304>(A, W, M_pad, N_pad, K, ep, st);
+        if (n256 && ep.kx == 3) return launch_persist<EPI, P_SCHED | P_X3IMG>(A, W, M_pad, N_pad, K, ep, st);
     }
     if constexpr (EPI == EPI_BIAS_F16 || EPI == EPI_GELU_F16) {
         if (n256 && (EPI == EPI_BIAS_F16 || ep.kx == 1)) {
-            constexpr int SLAB = EPI == EPI_BIAS_F16 ? 1048576 : 0;
-            return persist_tagged<EPI, 786432 | SLAB>(tag, A, W, M_pad, N_pad, K, ep, st);
+            constexpr int SLAB = EPI == EPI_BIAS_F16 ? P_SLAB : 0;
+            return persist_tagged<EPI, P_SCHED | SLAB>(tag, A, W, M_pad, N_pad, K, ep, st);
         }
-        if (n256) return launch_t<256, 256, 2, 4, 2, 64, EPI, 192 | 8192>(A, W, M_pad, N_pad, K, ep, st);
-        return launch_t<256, 128, 4, 2, 3, 64, EPI, 192 | 8192>(A, W, M_pad, N_pad, K, ep, st);
-    } else if constexpr (EPI == EPI_LSE) {
-        if (n256) return launch_t<256, 256, 2, 4, 2, 64, EPI, 128>(A, W, M_pad, N_pad, K, ep, st);
-        return launch_t<256, 128, 4, 2, 3, 64, EPI, 128>(A, W, M_pad, N_pad, K, ep, st);
-    } else {
-        if (n256) return launch_t<256, 256, 2, 4, 2, 64, EPI, 128 | 8192>(A, W, M_pad, N_pad, K, ep, st);
-        return launch_t<256, 128, 4, 2, 3, 64, EPI, 128 | 8192>(A, W, M_pad, N_pad, K, ep, st);
     }
+    if (n256) return launch_t<256, 256, 2, 4, 2, 64, EPI>(A, W, M_pad, N_pad, K, ep, st);
+    return launch_t<256, 128, 4, 2, 3, 64, EPI>(A, W, M_pad, N_pad, K, ep, st);
 }
 
 }  // namespace
@@ -1780,7 +1767,7 @@ int gemm_lnres_workgroups(int N_pad) {
 
 // Production split-operand fp16x3 GEMM (gemm_x3s_kernel; tools/x3s_epi_probe.py).
 // Stamp builds (RS_DIAG only, rs_debug_stamps): while g_stamps is set, every split-operand GEMM
-// launch runs the VAR 268435456 build of its kernel and adds its per-workgroup phase cycles into
+// launch runs the X_DIAG_STAMP build of its kernel and adds its per-workgroup phase cycles into
 // the region of its instance: 0 QKV / fp32 out, 1 BertIntermediate (GELU image), 2 O-projection +
 // LayerNorm, 3 BertOutput + LayerNorm (each [256 workgroups][16 words]).
 #if RS_DIAG
@@ -1799,11 +1786,10 @@ hipError_t launch_gemm_x3s_v(int epi, const f16* A, const f16* W, int ldw, int M
         case EPI_BIAS_F32: return launch_x3s<EPI_BIAS_F32, STV>(A, W, M_pad, N_pad, K, ep, st, ldw);
         case EPI_GELU_F16: return launch_x3s<EPI_GELU_F16, STV>(A, W, M_pad, N_pad, K, ep, st, ldw);
         case EPI_LNRES_IMG: {
-            // Output columns permuted inside 32-column groups (VAR 16777216: 16-B epilogue loads,
-            // +1.1 % end to end, profiles/r3p2_lnperm_ab.txt); VAR 67108864 is a name tag only (the
-            // BertOutput launch, K = 3072), so rocprofv3 reports the two instances separately.
+            // X_TAG_FFN2 is a name tag only (the BertOutput launch, K = 3072), so rocprofv3 reports
+            // the two instances separately.
             // Gang formation (RS_LNGANG, read per call; lnr_gang_ticket): "xcd" (default) = start-order
-            // tickets inside each XCD (VAR 134217728; a panel's column tiles share one L2), the rest
+            // tickets inside each XCD (X_GANG_XCD; a panel's column tiles share one L2), the rest
             // from an overflow ticket; "ticket" = consecutive start-order tickets.  Either way a
             // gang's members have all started before it exchanges statistics.  The exchange needs
             // ntn (= N_pad / 256) workgroups of the gang co-resident — anywhere on the GPU for
@@ -1814,17 +1800,12 @@ hipError_t launch_gemm_x3s_v(int epi, const f16* A, const f16* W, int ldw, int M
             // workgroups co-resident anywhere instead of on one XCD.
             const char* g = getenv("RS_LNGANG");
             const bool xcd = !(g && !strcmp(g, "ticket"));
-            // VAR 1073741824: the next tile's stage 0 issued after the row statistics (O-projection
-            // -1.1 %, BertOutput -0.7 %, profiles/r5late0_stage0_after_stats.txt)
-            // VAR 4: the residual by whole-line LDS-DMA (round 6: O-projection -1.9 %, BertOutput -1.0 %,
-            // C3 +0.4 %, bitwise; profiles/r6o_lnres_residual_dma.txt)
-            constexpr int VL = 16777216 | 1073741824 | 4 | STV;
             if (xcd) {
-                if (K > 1024) return launch_x3s<EPI_LNRES_IMG, VL | 67108864 | 134217728>(A, W, M_pad, N_pad, K, ep, st, ldw);
-                return launch_x3s<EPI_LNRES_IMG, VL | 134217728>(A, W, M_pad, N_pad, K, ep, st, ldw);
+                if (K > 1024) return launch_x3s<EPI_LNRES_IMG, STV | X_TAG_FFN2 | X_GANG_XCD>(A, W, M_pad, N_pad, K, ep, st, ldw);
+                return launch_x3s<EPI_LNRES_IMG, STV | X_GANG_XCD>(A, W, M_pad, N_pad, K, ep, st, ldw);
             }
-            if (K > 1024) return launch_x3s<EPI_LNRES_IMG, VL | 67108864>(A, W, M_pad, N_pad, K, ep, st, ldw);
-            return launch_x3s<EPI_LNRES_IMG, VL>(A, W, M_pad, N_pad, K, ep, st, ldw);
+            if (K > 1024) return launch_x3s<EPI_LNRES_IMG, STV | X_TAG_FFN2>(A, W, M_pad, N_pad, K, ep, st, ldw);
+            return launch_x3s<EPI_LNRES_IMG, STV>(A, W, M_pad, N_pad, K, ep, st, ldw);
         }
     }
     return hipErrorInvalidValue;
@@ -1836,7 +1817,7 @@ hipError_t launch_gemm_x3s(int epi, const f16* A, const f16* W, int ldw, int M_p
     // the buffer descriptors address one 256-row panel: 32-bit byte offsets
     if ((long long)256 * ldw * 2 >= (1ll << 31) || (long long)256 * 2 * K * 2 >= (1ll << 31)) return hipErrorInvalidValue;
 #if RS_DIAG
-    if (g_stamps) return launch_gemm_x3s_v<268435456>(epi, A, W, ldw, M_pad, N_pad, K, ep, st);
+    if (g_stamps) return launch_gemm_x3s_v<X_DIAG_STAMP>(epi, A, W, ldw, M_pad, N_pad, K, ep, st);
 #endif
     return launch_gemm_x3s_v<0>(epi, A, W, ldw, M_pad, N_pad, K, ep, st);
 }
@@ -1877,7 +1858,7 @@ hipError_t launch_gemm(int epi, const f16* A, const f16* W, int M_pad, int N_pad
 }
 
 // Timing/diagnostic entry (not part of the scoring path): one GEMM with an explicit tile
-// configuration and VAR bits, C = A[M,K].W[N,K]^T + bias -> fp16 [M, N].
+// configuration (cfg) and variant (dbg), C = A[M,K].W[N,K]^T + bias -> fp16 [M, N].
 extern "C" int rs_debug_gemm(int cfg, int dbg, const void* A, const void* W, const float* bias, void* out,
                              int M, int N, int K, void* stream) {
     EpiArgs ep{};
@@ -1897,15 +1878,15 @@ extern "C" int rs_debug_gemm(int cfg, int dbg, const void* A, const void* W, con
         if (cfg == 31) ep.ldc = 2 * N;
         if (dbg == 0) e = launch_gemm_x3s(epi, a, w, 2 * K, M, N, K, ep, st);
 #if RS_DIAG
-#define RS_X3(VAR_)                                                                        \
-    (cfg == 31 ? launch_x3s<EPI_GELU_F16, VAR_>(a, w, M, N, K, ep, st) : launch_x3s<EPI_BIAS_F32, VAR_>(a, w, M, N, K, ep, st))
+#define RS_X3(OPT_)                                                                        \
+    (cfg == 31 ? launch_x3s<EPI_GELU_F16, OPT_>(a, w, M, N, K, ep, st) : launch_x3s<EPI_BIAS_F32, OPT_>(a, w, M, N, K, ep, st))
         else switch (dbg) {
-            case 1: e = RS_X3(1); break;
-            case 2: case 20: case 52: e = RS_X3(2); break;
-            case 3: e = RS_X3(3); break;
-            case 50: e = RS_X3(8); break;
-            case 51: e = RS_X3(33554432); break;
-            case 53: e = RS_X3(8 | 33554432); break;
+            case 1: e = RS_X3(X_DIAG_NOSTAGE); break;
+            case 2: case 20: case 52: e = RS_X3(X_DIAG_NOSTORE); break;
+            case 3: e = RS_X3(X_DIAG_NOSTAGE | X_DIAG_NOSTORE); break;
+            case 50: e = RS_X3(X_DIAG_NOWAIT); break;
+            case 51: e = RS_X3(X_DIAG_PANEL0); break;
+            case 53: e = RS_X3(X_DIAG_NOWAIT | X_DIAG_PANEL0); break;
             default: return -1;
         }
 #undef RS_X3
@@ -1915,16 +1896,17 @@ extern "C" int rs_debug_gemm(int cfg, int dbg, const void* A, const void* W, con
         return e == hipSuccess ? 0 : -2;
     }
     // fp16 kernels: 9 / 11 persistent bias / GELU with the plain schedule (the bitwise reference
-    // of the production schedule), 21 / 18 the production persistent schedules, 0 (dbg 8384) the
-    // pipelined kernel with non-temporal stores
+    // of the production schedule), 21 / 18 the production persistent schedules, 0 the pipelined
+    // kernel's bias epilogue (16x16x32, non-temporal stores; dbg must be 8384, the number its
+    // callers have always passed — it selects nothing)
     switch (cfg) {
         case 9: e = launch_persist<EPI_BIAS_F16>(a, w, M, N, K, ep, st); break;
         case 11: e = launch_persist<EPI_GELU_F16>(a, w, M, N, K, ep, st); break;
-        case 21: e = launch_persist<EPI_BIAS_F16, 786432 | 1048576>(a, w, M, N, K, ep, st); break;
-        case 18: e = launch_persist<EPI_GELU_F16, 262144 | 524288>(a, w, M, N, K, ep, st); break;
+        case 21: e = launch_persist<EPI_BIAS_F16, P_SCHED | P_SLAB>(a, w, M, N, K, ep, st); break;
+        case 18: e = launch_persist<EPI_GELU_F16, P_SCHED>(a, w, M, N, K, ep, st); break;
         case 0:
             if (dbg != 8384) return -1;
-            e = launch_t<256, 256, 2, 4, 2, 64, EPI_BIAS_F16, 8384>(a, w, M, N, K, ep, st);
+            e = launch_t<256, 256, 2, 4, 2, 64, EPI_BIAS_F16>(a, w, M, N, K, ep, st);
             break;
         default: return -1;
     }

@@ -23,8 +23,9 @@ from x3s_image import _split2, _unsplit2, gemm_ref
 
 pytestmark = pytest.mark.gpu
 
-# rs_debug_gemm cfg: 9 / 11 persistent bias / GELU, VAR 0; 21 bias, 18 GELU = production schedule;
-# 0 with dbg 8384 = pipelined plain kernel (16x16x32, non-temporal stores)
+# rs_debug_gemm cfg: 9 / 11 persistent bias / GELU, no options (the plain schedule); 21 bias
+# (P_SCHED | P_SLAB), 18 GELU (P_SCHED) = production schedule; 0 with dbg 8384 = pipelined plain
+# kernel (16x16x32, non-temporal stores)
 SHAPES = [("qkv", 2304, 768, False), ("oproj", 768, 768, False), ("ffn1", 3072, 768, True),
           ("ffn2", 768, 3072, False)]
 

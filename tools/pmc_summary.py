@@ -20,8 +20,8 @@ import sys
 
 EPI_N = {0: ("qkv", 2304), 1: ("ffn1", 3072), 3: ("res_f32", 768), 6: ("ffn2", 768),
          2: ("head_transform", 768), 4: ("decoder", 21248)}
-OPROJ_TAG = 65536          # VAR bit of the O-projection instance of the persistent kernel
-FFN2_TAG = 131072          # VAR bit of the BertOutput instance (fp16-output FFN2, RS_LNRES_DEFER=2)
+OPROJ_TAG = 65536          # k_gemm.hip P_TAG_OPROJ: the O-projection instance of the persistent kernel
+FFN2_TAG = 131072          # k_gemm.hip P_TAG_FFN2: the BertOutput instance (fp16-output FFN2, RS_LNRES_DEFER=2)
 RE_GEMM = re.compile(r"gemm_f16_kernelILi(\d+)ELi(\d+)ELi\d+ELi\d+ELi\d+ELi\d+ELi(\d+)E")
 RE_PERSIST = re.compile(r"gemm_persist_kernelILi(\d+)ELi(\d+)E")
 RE_X3S = re.compile(r"gemm_x3s_kernelILi(\d+)ELi(\d+)E")
