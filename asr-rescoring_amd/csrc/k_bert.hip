@@ -1281,7 +1281,7 @@ extern "C" int rs_debug_attention(int kind, const void* qkv, const int* len, con
 }
 
 // Test entry (not part of the scoring path): the production attention router on fp32 Q/K/V
-// [rows, 3H] over sequences [0, n_seq) — launch_attention_full as run_chunk calls it for a
+// [rows, 3H] over sequences [0, n_seq) — launch_attention_full as rs_api.hip's layer_split calls it for a
 // split-operand layer without dedup (kx = 2: ctx the interleaved two-part image [rows, 2H]).
 // max_len: the longest sequence of the launch (<= 48 / <= 64: attn16x3v2_kernel with 48 / 64 staged
 // key rows; above: the mixed chunk, attn16x3v2_kernel<64> and attn_full_kernel<float> each skipping

@@ -1759,7 +1759,7 @@ size_t lnres_counter_bytes() { return lnr_counter_bytes(); }
 // Workgroups of one fused residual + LayerNorm GEMM launch (EPI_LNRES_IMG): whole gangs of the
 // N_pad / 256 column tiles of a row panel, at one workgroup per CU.  A launch over P row panels
 // runs ceil(P / gangs) rounds of panels, so the host cuts its chunks at multiples of
-// 256 * gangs rows (run_all).
+// 256 * gangs rows (rs_api.hip chunk_cap).
 int gemm_lnres_workgroups(int N_pad) {
     const int ntn = N_pad / 256, cus = n_cus() / 8 * 8;
     return ntn > 0 ? cus / ntn * ntn : 0;
@@ -1919,7 +1919,7 @@ extern "C" int rs_debug_gemm(int cfg, int dbg, const void* A, const void* W, con
 // [M_pad, ldc] (ldc >= N: a column window of a wider buffer); EPI_GELU_F16: out the two-part image
 // [M_pad, ldc] (ldc >= 2N); EPI_LNRES_IMG: out the residual image [M_pad, 2N], rewritten in place
 // with image(LN(A.W^T + bias + out; gamma, beta, eps)), lnx / lncnt / lnerr the caller's buffers
-// (sizes: rs_debug_lnres_sizes; zeroed once by the caller), as rs_api.hip's lnres_ep passes them.
+// (sizes: rs_debug_lnres_sizes; zeroed once by the caller), as rs_api.hip's split_block passes them.
 extern "C" int rs_debug_x3s(int epi, const void* A2, const void* W2, const float* bias, const float* gamma,
                             const float* beta, float eps, void* out, int ldc, int M_pad, int m_valid, int N, int K,
                             void* lnx, void* lncnt, void* lnerr, void* stream) {

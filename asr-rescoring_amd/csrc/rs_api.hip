@@ -65,6 +65,36 @@ struct Chunk {
     int max_len = 0;   // longest sequence of the chunk (attention kernel choice)
 };
 
+// Pinned staging buffer (int words) of one asynchronous upload per call: the next call waits for
+// the previous upload's event before it overwrites the buffer.  The event is created at first use.
+struct Staging {
+    int* p = nullptr;
+    size_t cap = 0;
+    hipEvent_t done = nullptr;
+    // waits for the previous upload and grows the buffer p to n ints
+    hipError_t begin(size_t n) {
+        hipError_t e = done ? hipEventSynchronize(done) : hipSuccess;
+        if (e == hipSuccess && n > cap) {
+            if (p) (void)hipHostFree(p);
+            p = nullptr;
+            e = hipHostMalloc((void**)&p, std::max<size_t>(n, 1) * 4, hipHostMallocDefault);
+            cap = e == hipSuccess ? n : 0;
+        }
+        return e;
+    }
+    // the first n ints -> dst (grown to hold them), asynchronously on st
+    hipError_t upload(DevBuf& dst, size_t n, hipStream_t st) {
+        hipError_t e = dst.ensure(std::max<size_t>(n, 1) * 4);
+        if (e == hipSuccess) e = hipMemcpyAsync(dst.p, p, n * 4, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && !done) e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
+        return e == hipSuccess ? hipEventRecord(done, st) : e;
+    }
+    ~Staging() {       // with the model (rs_model_destroy, on the model's device)
+        if (p) (void)hipHostFree(p);
+        if (done) (void)hipEventDestroy(done);
+    }
+};
+
 }  // namespace
 
 struct rs_model {
@@ -90,19 +120,14 @@ struct rs_model {
     DevBuf lnx, lncnt, lnerr;   // EPI_LNRES_IMG: per-tile row statistics, gang-ticket words (left
                                 // zeroed by every launch), sticky statistics-wait timeout flag
     DevBuf ctxq, resq, tq32, hq32, hq16, interq, lab, llog, part, rowlp_tmp;
-    DevBuf meta, hypoff;
+    DevBuf meta;
     f16* emb_dst = nullptr;     // MODE_EMB output (rs_token_embed / rs_bertscore_recall)
     DevBuf emb, plan;           // rs_bertscore_recall: token embeddings, work-item plan
     DevBuf flag;                // non-finite-output flag of the last scoring call(s) (range guard)
     bool sync_check = true;     // scoring calls synchronise and report their flags (rs_model_set_sync_check)
     int* pinned_flag = nullptr;
-    int* pinned_plan = nullptr;
-    size_t pinned_plan_cap = 0;
-    hipEvent_t plan_done = nullptr;
-    std::vector<int> pinned_dummy;
-    int* pinned = nullptr;
-    size_t pinned_cap = 0;
-    hipEvent_t upload_done = nullptr;
+    // metadata (run_all) and BERTScore plan uploads: rs_bertscore_recall does both in one call, and
+    Staging stage_meta, stage_plan;   // a shared buffer would make it wait on the host in between
     // call ordering across streams: the end of the last call's work (any stream); a call on another
     // stream first makes its stream wait for it (CallOrder)
     hipEvent_t call_done = nullptr;
@@ -122,6 +147,16 @@ struct rs_model {
 
 namespace {
 
+// Tail of the weight uploads: allocate, remember (freed by rs_model_destroy), copy.
+void* to_device(rs_model* m, const void* src, size_t bytes, hipError_t* err) {
+    void* p = nullptr;
+    *err = hipMalloc(&p, bytes);
+    if (*err != hipSuccess) return nullptr;
+    m->allocs.push_back(p);
+    *err = hipMemcpy(p, src, bytes, hipMemcpyHostToDevice);
+    return p;
+}
+
 // Weight W [rows, cols] (nn.Linear [out, in]) -> fp16 operand image [rows_pad, kx*cols]:
 // kx == 1: [hi]; kx == 3: [hi | lo*64 | hi/64] (pairs with the activation image
 // [hi | hi/64 | lo*64], common.h put_split: the factors keep lo out of the fp16 subnormals).
@@ -140,12 +175,7 @@ f16* upload_f16(rs_model* m, const std::vector<float>& src, size_t rows_pad, siz
                 row[2 * cols + c] = (f16)((float)hi * (1.f / 64.f));
             }
         }
-    void* p = nullptr;
-    *err = hipMalloc(&p, tmp.size() * sizeof(f16));
-    if (*err != hipSuccess) return nullptr;
-    m->allocs.push_back(p);
-    *err = hipMemcpy(p, tmp.data(), tmp.size() * sizeof(f16), hipMemcpyHostToDevice);
-    return (f16*)p;
+    return (f16*)to_device(m, tmp.data(), tmp.size() * sizeof(f16), err);
 }
 
 // Weight W [rows, cols] -> the split-operand GEMM's interleaved two-part image [rows, 2 cols]
@@ -162,12 +192,7 @@ f16* upload_il(rs_model* m, const std::vector<float>& src, size_t cols, hipError
             row[il_hi((int)c)] = hi;
             row[il_hi((int)c) + 32] = (f16)((v - (float)hi) * 64.f);
         }
-    void* p = nullptr;
-    *err = hipMalloc(&p, tmp.size() * sizeof(f16));
-    if (*err != hipSuccess) return nullptr;
-    m->allocs.push_back(p);
-    *err = hipMemcpy(p, tmp.data(), tmp.size() * sizeof(f16), hipMemcpyHostToDevice);
-    return (f16*)p;
+    return (f16*)to_device(m, tmp.data(), tmp.size() * sizeof(f16), err);
 }
 
 // The split-operand K loop forms 64 W_hi in fp16 (k_gemm.hip kstep16): finite only for
@@ -182,12 +207,7 @@ bool x3s_range_ok(const std::vector<float>& v) {
 float* upload_f32(rs_model* m, const std::vector<float>& src, size_t n_pad, hipError_t* err) {
     std::vector<float> tmp(std::max(n_pad, src.size()), 0.0f);
     std::memcpy(tmp.data(), src.data(), src.size() * sizeof(float));
-    void* p = nullptr;
-    *err = hipMalloc(&p, tmp.size() * sizeof(float));
-    if (*err != hipSuccess) return nullptr;
-    m->allocs.push_back(p);
-    *err = hipMemcpy(p, tmp.data(), tmp.size() * sizeof(float), hipMemcpyHostToDevice);
-    return (float*)p;
+    return (float*)to_device(m, tmp.data(), tmp.size() * sizeof(float), err);
 }
 
 // The fp16 operand images (fp16 and fp16x3 modes) hold |x| <= 65504: a weight beyond it
@@ -293,19 +313,26 @@ struct CallOrder {
         }
     }
 };
+// Opening of every entry point that enqueues work: the model's device, then the call ordering.
 #define CALL_ORDER(m_, st_)                                   \
+    HIPTRY(hipSetDevice(m_->device));                         \
     if (int r_ = order_begin((m_), (st_))) return r_;         \
     CallOrder order_((m_), (st_))
+
+// Row count padded to the GEMM kernels' row alignment.
+int pad_rows(int64_t rows) {
+    const int al = gemm_row_align();
+    return (int)((rows + al - 1) / al * al);
+}
 
 int reserve_impl(rs_model* m, int64_t max_rows) {
     const rs_bert_cfg& c = m->cfg;
     if (max_rows < 512) return fail(RS_EARG, "max_rows must be >= 512");
     if (max_rows > (int64_t)1 << 26) return fail(RS_EARG, "max_rows too large");
-    const int al = gemm_row_align();
     m->max_rows = max_rows;
-    m->m_pad = (int)((max_rows + al - 1) / al * al);
+    m->m_pad = pad_rows(max_rows);
     m->s_cap = (int)(max_rows / 3) + 1;
-    m->r_pad = (m->s_cap + al - 1) / al * al;
+    m->r_pad = pad_rows(m->s_cap);
     const size_t M = m->m_pad, R = m->r_pad, H = c.hidden, F = c.intermediate;
     HIPTRY(hipSetDevice(m->device));
     const size_t kx = m->kx;
@@ -392,305 +419,293 @@ struct ProfScope {
     }
 };
 
-int gemm(rs_model* m, hipStream_t st, int kind, int epi, const f16* A, const f16* W, int m_valid,
-         int N_pad, int K, EpiArgs ep, int n_flop_cols) {
-    const int al = gemm_row_align();
-    const int M_pad = (m_valid + al - 1) / al * al;
-    ep.m_valid = m_valid;
-    ProfScope ps(m, st, kind, 2.0 * m_valid * (double)n_flop_cols * K);
-    HIPTRY(launch_gemm(epi, A, W, M_pad, N_pad, K, ep, st, kind == RS_K_OPROJ ? 1 : kind == RS_K_FFN2 ? 2 : 0));
-    return RS_OK;
-}
+// One launch under a profile scope of its own, no flops recorded (m, st: the caller's).
+#define LAUNCH(kind_, call_) do { ProfScope ps_(m, st, (kind_), 0); HIPTRY(call_); } while (0)
+#define LAUNCH_OTHER(call_) LAUNCH(RS_K_OTHER, call_)
 
 enum Mode { MODE_MLM = 0, MODE_CLS = 1, MODE_EMB = 2 };
 
-// RS_OPROJ: "f16" (default in the fp16 precision mode: fp16-output O projection + fused
-// residual/LayerNorm rows kernel) or "resln" (residual rebuilt in the GEMM's accumulators)
-// (read per call, like RS_DEDUP, so a test can flip it in-process)
-bool oproj_f16() {
-    const char* e = getenv("RS_OPROJ");
-    return !(e && !strcmp(e, "resln"));
-}
-// RS_LNRES_DEFER (fp16 mode, O-projection split): ln_res_rows writes only the statistics and
-// the fp16 image of the post-attention stream x = LN0(x32) + o1 (o1 = fp16 O-projection
-// output), so x never round-trips through HBM in fp32, and x is rebuilt downstream:
-//   2 (default): BertOutput is a lean fp16-output GEMM (o2) and one second ln_res_rows pass
-//                forms LN2(LN1(LN0(x32) + o1) + o2) — no residual traffic in any GEMM epilogue;
-//   1: the BertOutput GEMM rebuilds x in its accumulator init (EpiArgs.res_o16) — slower: the
-//      extra loads sit in front of the tile's first MFMA;
-//   0: ln_res_rows writes x back into x32 and BertOutput reads it (EPI_RESLN_F32).
-int lnres_defer() {
-    const char* e = getenv("RS_LNRES_DEFER");
-    return e ? atoi(e) : 2;
-}
-// RS_FFN2: "resln" (default) or "f16" (the O-projection split applied to BertOutput)
-bool ffn2_f16() {
-    const char* e = getenv("RS_FFN2");
-    return e && !strcmp(e, "f16");
+// The environment switches of one scoring call: read once (call_opts, at the top of run_all) and
+// passed down, so that the chunk cap, the dedup plan and the chunk runner see the same resolved
+// forms.  Read per call, not once per process, so that a test can flip a switch in-process.
+struct CallOpts {
+    bool lastq, dedup, chunk_align;
+    int ln_diag;
+    // the layer forms that run, resolved against the model's precision mode, weights and shape
+    bool x3s, imgres, lnfuse, x3_dedup;   // fp16x3
+    bool oproj_f16, ffn2_f16;             // fp16
+    int lnres_defer;                      // fp16: 0, 1 or 2; 0 where there is no fp16 O output to defer
+};
+
+CallOpts call_opts(const rs_model* m) {
+    const rs_bert_cfg& cf = m->cfg;
+    auto is = [](const char* name, const char* v) { const char* e = getenv(name); return e && !strcmp(e, v); };
+    auto num = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+    CallOpts o{};
+    // RS_LASTQ: "0" = full Q/K/V GEMM at the last layer (default: Q of the scored rows only)
+    o.lastq = !is("RS_LASTQ", "0");
+    // RS_DEDUP (default 1): layer-0 dedup (plan_unique_rows): MLM mode, fp16 operands (or the
+    // fp16x3 form below), >= 2 layers (layer 0 is not the query-only layer)
+    o.dedup = num("RS_DEDUP", 1) != 0;
+    // RS_CHUNK_ALIGN: "0" = chunks of max_rows (default: whole LayerNorm-gang rounds, chunk_cap)
+    o.chunk_align = !is("RS_CHUNK_ALIGN", "0");
+    // RS_OPROJ: "f16" (default in the fp16 precision mode: fp16-output O projection + fused
+    // residual/LayerNorm rows kernel) or "resln" (residual rebuilt in the GEMM's accumulators)
+    o.oproj_f16 = m->kx == 1 && !is("RS_OPROJ", "resln");
+    // RS_FFN2: "resln" (default) or "f16" (the O-projection split applied to BertOutput)
+    o.ffn2_f16 = m->kx == 1 && is("RS_FFN2", "f16");
+    // RS_LNRES_DEFER (fp16 mode, O-projection split): ln_res_rows writes only the statistics and
+    // the fp16 image of the post-attention stream x = LN0(x32) + o1 (o1 = fp16 O-projection
+    // output), so x never round-trips through HBM in fp32, and x is rebuilt downstream:
+    //   2 (default): BertOutput is a lean fp16-output GEMM (o2) and one second ln_res_rows pass
+    //                forms LN2(LN1(LN0(x32) + o1) + o2) — no residual traffic in any GEMM epilogue;
+    //   1: the BertOutput GEMM rebuilds x in its accumulator init (EpiArgs.res_o16) — slower: the
+    //      extra loads sit in front of the tile's first MFMA;
+    //   0: ln_res_rows writes x back into x32 and BertOutput reads it (EPI_RESLN_F32).
+    const int defer = num("RS_LNRES_DEFER", 2);
+    o.lnres_defer = !o.oproj_f16 || o.ffn2_f16 || defer == 0 ? 0 : defer == 2 ? 2 : 1;
+    // RS_LNFUSE_DIAG=8 (tests): every statistics / gang wait times out at once (the RS_EHIP
+    // path); no other bit is honoured (no diagnostic changes scores)
+    o.ln_diag = num("RS_LNFUSE_DIAG", 0) & 8;
+    // RS_X3S (fp16x3 mode, default 1): the encoder projections run as split-operand GEMMs
+    // (gemm_x3s_kernel: two-part activation images, three fp16 products formed in registers, fp32
+    // outputs + ln_res32 rows for the residual blocks); 0 = the K-concatenated three-part form.
+    o.x3s = m->kx == 3 && !is("RS_X3S", "0") && m->x3s_w && cf.hidden % 256 == 0 && cf.intermediate % 256 == 0;
+    // RS_X3S_IMGRES (split-operand layers, default 1): the residual stream is held only as the
+    // two-part image of the normalised hidden state (ln_res_img: 12 B per element per residual
+    // block, no fp32 pre-LN stream or statistics); 0 = ln_res32 over the fp32 pre-LN stream.
+    o.imgres = o.x3s && !is("RS_X3S_IMGRES", "0");
+    // RS_LNFUSE (image-held residual; default 1): the residual add + LayerNorm of both blocks run in
+    // the O-projection / BertOutput GEMM epilogues (EPI_LNRES_IMG: full rows through an in-launch
+    // exchange of row statistics) instead of as ln_res_img passes (RS_LNFUSE=0).
+    o.lnfuse = o.imgres && !is("RS_LNFUSE", "0") && cf.hidden % 256 == 0 && cf.hidden <= 1024;
+    // fp16x3 layer-0 dedup: the split-operand layer with the image-held residual (its attention
+    // kernel reads the unique rows for chunks with T <= 64)
+    o.x3_dedup = o.imgres;
+    return o;
 }
 
-// RS_X3S (fp16x3 mode, default 1): the encoder projections run as split-operand GEMMs
-// (gemm_x3s_kernel: two-part activation images, three fp16 products formed in registers, fp32
-// outputs + ln_res32 rows for the residual blocks); 0 = the K-concatenated three-part form.
-// Read per call (tests flip it in-process).
-bool x3s_on(const rs_model* m) {
-    const char* e = getenv("RS_X3S");
-    return !(e && !strcmp(e, "0")) && m->x3s_w && m->cfg.hidden % 256 == 0 && m->cfg.intermediate % 256 == 0;
-}
-// RS_X3S_IMGRES (split-operand layers, default 1): the residual stream is held only as the
-// two-part image of the normalised hidden state (ln_res_img: 12 B per element per residual
-// block, no fp32 pre-LN stream or statistics); 0 = ln_res32 over the fp32 pre-LN stream.
-bool x3s_imgres_on() {
-    const char* e = getenv("RS_X3S_IMGRES");
-    return !(e && !strcmp(e, "0"));
-}
-// RS_LNFUSE (image-held residual; default 1): the residual add + LayerNorm of both blocks run in
-// the O-projection / BertOutput GEMM epilogues (EPI_LNRES_IMG: full rows through an in-launch
-// exchange of row statistics) instead of as ln_res_img passes (RS_LNFUSE=0).  Read per call.
-bool lnfuse_on(const rs_bert_cfg& cf) {
-    const char* e = getenv("RS_LNFUSE");
-    return !(e && !strcmp(e, "0")) && cf.hidden % 256 == 0 && cf.hidden <= 1024;
-}
-
-// Runs the encoder + head over sequences [c.s0, c.s1) (one chunk).
-int run_chunk(rs_model* m, hipStream_t st, const int* d_tok, const SeqMeta& sm, const Chunk& c,
-              int mode, float* d_out_rows /* indexed by sequence */) {
+// One chunk's run of the encoder + head over sequences [c.s0, c.s1): what the call fixed, and the
+// typed workspace pointers.  Aggregate: the first seven members are given, the rest follow.
+struct ChunkCtx {
+    rs_model* m;
+    hipStream_t st;
+    const int* d_tok;
+    const SeqMeta& sm;
+    const Chunk& c;
+    const CallOpts& o;
+    int mode;
     const rs_bert_cfg& cf = m->cfg;
     const int H = cf.hidden, F = cf.intermediate, nh = cf.heads, kx = m->kx;
+    const float eps = cf.ln_eps;
     const bool q32 = kx == 3;                 // fp16x3: QKV kept in fp32 for attention
-    const int qkv_epi = q32 ? EPI_BIAS_F32 : EPI_BIAS_F16;
+    const int qkv_epi = q32 ? EPI_BIAS_F32 : EPI_BIAS_F16;   // (split-operand layers are fp16x3: fp32)
     const int rows = c.rows, ns = c.s1 - c.s0;
     const bool dedup = c.urows > 0;           // layer-0 Q/K/V over unique rows (MLM; fp16, or fp16x3 split)
-    const bool x3s = kx == 3 && x3s_on(m);    // split-operand GEMMs: full-row images are two-part
-    const int kxf = x3s ? 2 : kx;             // width factor of the full-row operand images
-    const bool imgres = x3s && x3s_imgres_on();  // residual stream = the two-part image in h16
-    const bool lnfuse = imgres && lnfuse_on(cf);  // ... closed in the residual GEMMs' epilogues
-    float2* xst = m->xst.as<float2>();
-    f16* h16 = m->h16.as<f16>();
-    float* t32 = m->t32.as<float>();     // residual stream, pre-LN fp32 (LN rebuilt from xst)
+    const int kxf = o.x3s ? 2 : kx;           // width factor of the full-row operand images (split: two-part)
+    float2 *xst = m->xst.as<float2>(), *xst1 = m->xst1.as<float2>();
+    float* t32 = m->t32.as<float>();          // residual stream, pre-LN fp32 (LN rebuilt from xst)
+    f16* h16 = m->h16.as<f16>();              // ... or, with imgres, its image here
     void* qkv = m->qkv.p;
-    f16* ctx = m->ctx.as<f16>();
-    f16* inter = m->inter.as<f16>();
-    {
+    f16 *ctx = m->ctx.as<f16>(), *inter = m->inter.as<f16>();
+    // one row per sequence (query-row-only layer and heads)
+    f16 *ctxq = m->ctxq.as<f16>(), *hq16 = m->hq16.as<f16>(), *interq = m->interq.as<f16>();
+    float *resq = m->resq.as<float>(), *tq = m->tq32.as<float>(), *hq32 = m->hq32.as<float>();
+
+    // One GEMM over m_valid rows (padded to the kernels' row alignment), profiled as `kind`.
+    // split: the split-operand kernel (A a two-part image, W rows of 2K halfs, K the logical depth:
+    // three fp16 products, 2·m·n·3K flops); else launch_gemm (K the operand images' width, 2·m·n·K).
+    int gemm(int kind, int epi, bool split, const f16* A, const f16* W, int m_valid, int N_pad, int K, EpiArgs ep,
+             int n_flop_cols) {
+        ep.m_valid = m_valid;
+        ProfScope ps(m, st, kind, 2.0 * m_valid * (double)n_flop_cols * (split ? 3.0 * K : K));
+        if (split) HIPTRY(launch_gemm_x3s(epi, A, W, 2 * K, pad_rows(m_valid), N_pad, K, ep, st));
+        else HIPTRY(launch_gemm(epi, A, W, pad_rows(m_valid), N_pad, K, ep, st,
+                                kind == RS_K_OPROJ ? 1 : kind == RS_K_FFN2 ? 2 : 0));
+        return RS_OK;
+    }
+    // out <- acc + bias (+ res: fp32 rows of the same layout)
+    EpiArgs bias_ep(const float* bias, void* out, int ldc, const float* res = nullptr) const {
+        EpiArgs e{};
+        e.bias = bias; e.out = out; e.ldc = ldc; e.res = res;
+        return e;
+    }
+    // GELU output as an operand image of width factor w
+    EpiArgs gelu_ep(const float* bias, f16* out, int w) const {
+        EpiArgs e = bias_ep(bias, out, w * F);
+        e.kx = w; e.nlog = F;
+        return e;
+    }
+    // residual GEMM: t32 <- acc + bias + LN(t32) (in place: a tile reads and writes only its own
+    // rows x columns), LN given by the statistics in xst and the LN parameters (lg, lb)
+    EpiArgs resln_ep(const float* bias, const float* lg, const float* lb) const {
+        EpiArgs e = bias_ep(bias, t32, H, t32);
+        e.res_stats = xst; e.res_g = lg; e.res_b = lb;
+        return e;
+    }
+    // LayerNorm that produced layer li's input (embeddings LN, or the previous BertOutput LN)
+    const float* prev_g(int li) const { return li ? m->layers[li - 1].g2 : m->eg; }
+    const float* prev_b(int li) const { return li ? m->layers[li - 1].be2 : m->eb; }
+    int embed() {
         ProfScope ps(m, st, RS_K_OTHER, 0);
         // dedup: the per-copy pass keeps only the fp32 residual + LN statistics; the layer-0
         // GEMM operand is built over the chunk's unique rows (plan_unique_rows)
         // (split-operand dedup: every copy row's image stays in h16 — it is the layer-0
         // residual — and the unique rows' image goes to the idle FFN buffer)
-        HIPTRY(launch_embed_ln(d_tok, sm, c.s0, c.s1, 0, cf.mask_id, cf.vocab, m->word32, m->pos32,
-                               m->type32, m->eg, m->eb, cf.ln_eps, H, imgres ? nullptr : t32, imgres ? nullptr : xst,
-                               dedup && !x3s ? nullptr : h16, kxf, st));
+        HIPTRY(launch_embed_ln(d_tok, sm, c.s0, c.s1, 0, cf.mask_id, cf.vocab, m->word32, m->pos32, m->type32, m->eg, m->eb,
+                               eps, H, o.imgres ? nullptr : t32, o.imgres ? nullptr : xst, dedup && !o.x3s ? nullptr : h16,
+                               kxf, st));
         if (dedup)
-            HIPTRY(launch_embed_unique(d_tok, sm, c.s0, c.s1, cf.mask_id, cf.vocab, m->word32, m->pos32,
-                                       m->type32, m->eg, m->eb, cf.ln_eps, H, x3s ? inter : h16, kxf, st));
-    }
-    EpiArgs ep{};
-    // split-operand GEMM over m_valid rows: A two-part image, W rows of ldw halfs; profiled as
-    // MFMA work (three products of logical K)
-    auto gx = [&](int kind, int epi, const f16* A, const f16* W, int ldw, int m_valid, int N, int K, EpiArgs e,
-                  int n_flop_cols) -> int {
-        const int al = gemm_row_align();
-        e.m_valid = m_valid;
-        ProfScope ps(m, st, kind, 2.0 * m_valid * (double)n_flop_cols * 3.0 * K);
-        const int M_pad = (m_valid + al - 1) / al * al;
-        HIPTRY(launch_gemm_x3s(epi, A, W, ldw, M_pad, N, K, e, st));
+            HIPTRY(launch_embed_unique(d_tok, sm, c.s0, c.s1, cf.mask_id, cf.vocab, m->word32, m->pos32, m->type32,
+                                       m->eg, m->eb, eps, H, o.x3s ? inter : h16, kxf, st));
         return RS_OK;
-    };
-    auto gelu_ep = [&](const float* bias, f16* out) {
-        EpiArgs e{};
-        e.bias = bias; e.out = out; e.ldc = kx * F; e.kx = kx; e.nlog = F;
-        return e;
-    };
-    // residual GEMM: t32 <- acc + bias + LN(t32) (in place: a tile reads and writes only its own
-    // rows x columns), LN given by the statistics in xst and the LN parameters (lg, lb)
-    auto resln_ep = [&](const float* bias, const float* lg, const float* lb) {
-        EpiArgs e{};
-        e.bias = bias; e.res = t32; e.res_stats = xst; e.res_g = lg; e.res_b = lb; e.out = t32; e.ldc = H;
-        return e;
-    };
-    for (int li = 0; li < cf.layers; ++li) {
+    }
+
+    // Q/K/V projection of layer li into qkv, in the layer's GEMM form (split-operand or plain).
+    // uq: over the chunk's unique rows (layer-0 dedup).  qrow: the query-row-only form, which
+    // leaves the dense Q in tq.
+    int qkv_proj(int li, bool last, bool uq, bool qrow) {
         const Layer& L = m->layers[li];
-        const bool last = mode != MODE_EMB && li == cf.layers - 1;   // query-row-only layer
-        // LayerNorm that produced this layer's input (embeddings LN, or the previous BertOutput LN)
-        const float* pg = li ? m->layers[li - 1].g2 : m->eg;
-        const float* pb = li ? m->layers[li - 1].be2 : m->eb;
-        ep = EpiArgs{};
-        ep.bias = L.bqkv; ep.out = qkv; ep.ldc = 3 * H;
-        const bool uq = dedup && li == 0;
-        const void* qdense = nullptr;
-        const char* lq_env = getenv("RS_LASTQ");      // "0": full Q/K/V GEMM at the last layer
-        if (last && !uq && !(lq_env && !strcmp(lq_env, "0"))) {
-            // Query-row-only layer: K and V for every row (rows H..3H of the fused weight,
-            // written into columns H..3H of qkv), Q only for the scored row of each sequence
-            // (gathered operand rows -> dense [sequence, H] in the idle tq32 buffer)
-            const size_t esz = q32 ? 4 : 2;
-            ep.bias = L.bqkv + H;
-            ep.out = (char*)qkv + H * esz;
-            if (x3s) {
-                if (int r = gx(RS_K_QKV, EPI_BIAS_F32, h16, L.iqkv + (size_t)H * 2 * H, 2 * H, rows, 2 * H, H, ep, 2 * H))
-                    return r;
-            } else if (int r = gemm(m, st, RS_K_QKV, qkv_epi, h16, L.wqkv + (size_t)H * kx * H, rows, 2 * H, kx * H, ep,
-                                    2 * H)) return r;
-            f16* hq16g = m->hq16.as<f16>();
-            {
-                ProfScope ps(m, st, RS_K_OTHER, 0);
-                HIPTRY(launch_gather_query_rows(h16, kxf * H, sm, c.s0, c.s1, 0, hq16g, st));
-            }
-            EpiArgs eq{};
-            eq.bias = L.bqkv; eq.out = m->tq32.p; eq.ldc = H;
-            if (x3s) {
-                if (int r = gx(RS_K_QKV, EPI_BIAS_F32, hq16g, L.iqkv, 2 * H, ns, H, H, eq, H)) return r;
-            } else if (int r = gemm(m, st, RS_K_QKV, qkv_epi, hq16g, L.wqkv, ns, H, kx * H, eq, H)) return r;
-            qdense = m->tq32.p;
-        } else if (x3s) {
-            if (int r = gx(RS_K_QKV, EPI_BIAS_F32, uq ? inter : h16, L.iqkv, 2 * H, uq ? c.urows : rows, 3 * H, H, ep,
-                           last ? 2 * H : 3 * H)) return r;
-        } else if (int r = gemm(m, st, RS_K_QKV, qkv_epi, h16, L.wqkv, uq ? c.urows : rows, 3 * H, kx * H, ep,
-                                last ? 2 * H : 3 * H)) return r;
-        if (!last && x3s) {
-            // fp16x3 split-operand layer: projections write fp32 (o32 in the dead QKV buffer),
-            // the residual blocks close in ln_res32 (x32 <- LN(x32) + o32, next two-part image)
-            {
-                ProfScope ps(m, st, RS_K_ATTN, 0);
-                HIPTRY(launch_attention_full(qkv, true, sm, c.s0, c.s1, 0, H, nh, ctx, 2, st, uq, c.max_len));
-            }
-            float* o32 = (float*)qkv;
-            // residual block: h16 <- image(LN(A·Wᵀ + b + h16)) in the GEMM epilogue (lnfuse), or
-            // an fp32 GEMM output closed by a separate residual + LayerNorm pass
-            auto lnres_ep = [&](const float* bias, const float* g, const float* be) {
-                EpiArgs e{};
-                e.bias = bias; e.out = h16; e.ldc = 2 * H; e.nlog = H; e.res_g = g; e.res_b = be;
-                e.ln_eps = cf.ln_eps; e.lnx = m->lnx.p; e.lncnt = m->lncnt.as<unsigned>();
-                e.lnerr = m->lnerr.as<unsigned>();
-                // RS_LNFUSE_DIAG=8 (tests; read per call): every statistics / gang wait times out at
-                // once (the RS_EHIP path); no other bit is honoured (no diagnostic changes scores)
-                e.diag = (getenv("RS_LNFUSE_DIAG") ? atoi(getenv("RS_LNFUSE_DIAG")) : 0) & 8;
-                return e;
-            };
-            if (lnfuse) {
-                if (int r = gx(RS_K_OPROJ, EPI_LNRES_IMG, ctx, L.io, 2 * H, rows, H, H, lnres_ep(L.bo, L.g1, L.be1), H))
-                    return r;
-            } else {
-                ep = EpiArgs{}; ep.bias = L.bo; ep.out = o32; ep.ldc = H;
-                if (int r = gx(RS_K_OPROJ, EPI_BIAS_F32, ctx, L.io, 2 * H, rows, H, H, ep, H)) return r;
-                ProfScope ps(m, st, RS_K_OTHER, 0);
-                if (imgres) HIPTRY(launch_ln_res_img(h16, o32, rows, L.g1, L.be1, cf.ln_eps, H, st));
-                else HIPTRY(launch_ln_res32(t32, xst, xst, pg, pb, o32, rows, L.g1, L.be1, cf.ln_eps, H, h16, 2, st));
-            }
-            ep = EpiArgs{}; ep.bias = L.b1; ep.out = inter; ep.ldc = 2 * F; ep.kx = 2; ep.nlog = F;
-            if (int r = gx(RS_K_FFN1, EPI_GELU_F16, h16, L.i1, 2 * H, rows, F, H, ep, F)) return r;
-            if (lnfuse) {
-                if (int r = gx(RS_K_FFN2, EPI_LNRES_IMG, inter, L.i2, 2 * F, rows, H, F, lnres_ep(L.b2, L.g2, L.be2), H))
-                    return r;
-            } else {
-                ep = EpiArgs{}; ep.bias = L.b2; ep.out = o32; ep.ldc = H;
-                if (int r = gx(RS_K_FFN2, EPI_BIAS_F32, inter, L.i2, 2 * F, rows, H, F, ep, H)) return r;
-                ProfScope ps(m, st, RS_K_OTHER, 0);
-                if (imgres) HIPTRY(launch_ln_res_img(h16, o32, rows, L.g2, L.be2, cf.ln_eps, H, st));
-                else HIPTRY(launch_ln_res32(t32, xst, xst, L.g1, L.be1, o32, rows, L.g2, L.be2, cf.ln_eps, H, h16, 2, st));
-            }
-        } else if (!last) {
-            {
-                ProfScope ps(m, st, RS_K_ATTN, 0);
-                HIPTRY(launch_attention_full(qkv, q32, sm, c.s0, c.s1, 0, H, nh, ctx, kx, st, uq, c.max_len));
-            }
-            const bool fp16_split = kx == 1 && oproj_f16();
-            const int dmode = fp16_split && !ffn2_f16() ? lnres_defer() : 0;
-            const bool defer = dmode != 0;
-            // O-projection output (fp16): the dead QKV buffer when the BertOutput GEMM reads it
-            // back (deferred residual: it must survive FFN1), else the (free) FFN1 buffer
-            f16* o16 = defer ? (f16*)qkv : inter;
-            if (fp16_split) {
-                // O projection as a persistent fp16-output GEMM; the residual add + LayerNorm
-                // move into ln_res_rows, off the GEMM's critical path
-                ep = EpiArgs{}; ep.bias = L.bo; ep.out = o16; ep.ldc = H;
-                if (int r = gemm(m, st, RS_K_OPROJ, EPI_BIAS_F16, ctx, L.wo, rows, H, H, ep, H)) return r;
-                ProfScope ps(m, st, RS_K_OTHER, 0);
-                HIPTRY(launch_ln_res_rows(t32, xst, defer ? m->xst1.as<float2>() : xst, pg, pb, o16, rows, L.g1, L.be1,
-                                          cf.ln_eps, H, h16, !defer, st));
-            } else {
-                ep = resln_ep(L.bo, pg, pb);
-                if (int r = gemm(m, st, RS_K_OPROJ, EPI_RESLN_F32, ctx, L.wo, rows, H, kx * H, ep, H)) return r;
-                ProfScope ps(m, st, RS_K_OTHER, 0);
-                HIPTRY(launch_ln_rows(t32, rows, L.g1, L.be1, cf.ln_eps, H, nullptr, xst, h16, kx, st));
-            }
-            ep = gelu_ep(L.b1, inter);
-            if (int r = gemm(m, st, RS_K_FFN1, EPI_GELU_F16, h16, L.w1, rows, F, kx * H, ep, F)) return r;
-            if (dmode == 2) {
-                // BertOutput as a persistent fp16-output GEMM into the (free) ctx buffer; both
-                // residual blocks of the layer are closed by one ln_res_rows pass
-                ep = EpiArgs{}; ep.bias = L.b2; ep.out = ctx; ep.ldc = H;
-                if (int r = gemm(m, st, RS_K_FFN2, EPI_BIAS_F16, inter, L.w2, rows, H, F, ep, H)) return r;
-                ProfScope ps(m, st, RS_K_OTHER, 0);
-                HIPTRY(launch_ln_res_rows(t32, xst, xst, pg, pb, o16, rows, L.g2, L.be2, cf.ln_eps, H, h16, true, st,
-                                          m->xst1.as<float2>(), L.g1, L.be1, ctx));
-            } else if (kx == 1 && ffn2_f16()) {
-                // same split for BertOutput: fp16-output GEMM into the (free) ctx buffer
-                ep = EpiArgs{}; ep.bias = L.b2; ep.out = ctx; ep.ldc = H;
-                if (int r = gemm(m, st, RS_K_FFN2, EPI_BIAS_F16, inter, L.w2, rows, H, F, ep, H)) return r;
-                ProfScope ps(m, st, RS_K_OTHER, 0);
-                HIPTRY(launch_ln_res_rows(t32, xst, xst, L.g1, L.be1, ctx, rows, L.g2, L.be2, cf.ln_eps, H, h16, true, st));
-            } else {
-                ep = resln_ep(L.b2, L.g1, L.be1);
-                if (defer) {
-                    ep.res_stats = m->xst1.as<float2>();
-                    ep.res_o16 = o16; ep.res_stats0 = xst; ep.res_g0 = pg; ep.res_b0 = pb;
-                }
-                if (int r = gemm(m, st, RS_K_FFN2, EPI_RESLN_F32, inter, L.w2, rows, H, kx * F, ep, H)) return r;
-                ProfScope ps(m, st, RS_K_OTHER, 0);
-                HIPTRY(launch_ln_rows(t32, rows, L.g2, L.be2, cf.ln_eps, H, nullptr, xst, h16, kx, st));
-            }
-        } else {
-            // last layer: only the scored row of every sequence (one row per sequence)
-            f16* ctxq = m->ctxq.as<f16>();
-            float* resq = m->resq.as<float>();
-            float* tq = m->tq32.as<float>();
-            float* hq32 = m->hq32.as<float>();
-            f16* hq16 = m->hq16.as<f16>();
-            f16* interq = m->interq.as<f16>();
-            {
-                ProfScope ps(m, st, RS_K_ATTN, 0);
-                HIPTRY(launch_attention_query(qkv, q32, t32, xst, pg, pb, sm, c.s0, c.s1, 0, H, nh, ctxq, resq, kx, st,
-                                              qdense, imgres ? h16 : nullptr));
-            }
-            ep = EpiArgs{}; ep.bias = L.bo; ep.res = resq; ep.out = tq; ep.ldc = H;
-            if (int r = gemm(m, st, RS_K_OPROJ, EPI_RES_F32, ctxq, L.wo, ns, H, kx * H, ep, H)) return r;
-            { ProfScope ps(m, st, RS_K_OTHER, 0); HIPTRY(launch_ln_rows(tq, ns, L.g1, L.be1, cf.ln_eps, H, hq32, nullptr, hq16, kx, st)); }
-            ep = gelu_ep(L.b1, interq);
-            if (int r = gemm(m, st, RS_K_FFN1, EPI_GELU_F16, hq16, L.w1, ns, F, kx * H, ep, F)) return r;
-            ep = EpiArgs{}; ep.bias = L.b2; ep.res = hq32; ep.out = tq; ep.ldc = H;
-            if (int r = gemm(m, st, RS_K_FFN2, EPI_RES_F32, interq, L.w2, ns, H, kx * F, ep, H)) return r;
-            { ProfScope ps(m, st, RS_K_OTHER, 0); HIPTRY(launch_ln_rows(tq, ns, L.g2, L.be2, cf.ln_eps, H, hq32, nullptr, hq16, kx, st)); }
-        }
+        const bool sp = o.x3s;
+        const f16* W = sp ? L.iqkv : L.wqkv;
+        const int K = sp ? H : kx * H, ldw = sp ? 2 * H : kx * H;   // GEMM depth as gemm() takes it; halfs per weight row
+        if (!qrow)
+            return gemm(RS_K_QKV, qkv_epi, sp, uq && sp ? inter : h16, W, uq ? c.urows : rows, 3 * H, K,
+                        bias_ep(L.bqkv, qkv, 3 * H), last ? 2 * H : 3 * H);
+        // K and V for every row (rows H..3H of the fused weight, written into columns H..3H of
+        // qkv), Q only for the scored row of each sequence (gathered operand rows -> dense
+        // [sequence, H] in the idle tq32 buffer)
+        if (int r = gemm(RS_K_QKV, qkv_epi, sp, h16, W + (size_t)H * ldw, rows, 2 * H, K,
+                         bias_ep(L.bqkv + H, (char*)qkv + H * (size_t)(q32 ? 4 : 2), 3 * H), 2 * H)) return r;
+        LAUNCH_OTHER(launch_gather_query_rows(h16, kxf * H, sm, c.s0, c.s1, 0, hq16, st));
+        return gemm(RS_K_QKV, qkv_epi, sp, hq16, W, ns, H, K, bias_ep(L.bqkv, tq, H), H);
     }
-    if (mode == MODE_EMB) {
-        const Layer& L = m->layers[cf.layers - 1];
-        ProfScope ps(m, st, RS_K_OTHER, 0);
-        HIPTRY(launch_embed_out(t32, xst, L.g2, L.be2, sm, c.s0, c.s1, 0, H, m->emb_dst, st, imgres ? h16 : nullptr,
-                                m->kx == 3));
+
+    // Residual block of the split-operand layer: h16 <- image(LN(A·Wᵀ + b + h16)) in the GEMM
+    // epilogue (lnfuse), or an fp32 GEMM output (o32 in the dead QKV buffer) closed by a separate
+    // residual + LayerNorm pass: ln_res_img on the image, or ln_res32 (x32 <- LN(x32; pg, pb) + o32,
+    // next two-part image) on the fp32 pre-LN stream.
+    int split_block(int kind, const f16* A, const f16* W, int K, const float* bias, const float* pg, const float* pb,
+                    const float* g, const float* be) {
+        if (o.lnfuse) {
+            EpiArgs e = bias_ep(bias, h16, 2 * H);
+            e.nlog = H; e.res_g = g; e.res_b = be; e.ln_eps = eps; e.lnx = m->lnx.p;
+            e.lncnt = m->lncnt.as<unsigned>(); e.lnerr = m->lnerr.as<unsigned>(); e.diag = o.ln_diag;
+            return gemm(kind, EPI_LNRES_IMG, true, A, W, rows, H, K, e, H);
+        }
+        float* o32 = (float*)qkv;
+        if (int r = gemm(kind, EPI_BIAS_F32, true, A, W, rows, H, K, bias_ep(bias, o32, H), H)) return r;
+        if (o.imgres) LAUNCH_OTHER(launch_ln_res_img(h16, o32, rows, g, be, eps, H, st));
+        else LAUNCH_OTHER(launch_ln_res32(t32, xst, xst, pg, pb, o32, rows, g, be, eps, H, h16, 2, st));
         return RS_OK;
     }
-    float* hq32 = m->hq32.as<float>();
-    f16* hq16 = m->hq16.as<f16>();
-    float* tq = m->tq32.as<float>();
-    if (mode == MODE_MLM) {
-        ep = EpiArgs{}; ep.bias = m->bt; ep.out = tq; ep.ldc = H;
-        if (int r = gemm(m, st, RS_K_DECODER, EPI_GELU_F32, hq16, m->wt, ns, H, kx * H, ep, H)) return r;
-        { ProfScope ps(m, st, RS_K_OTHER, 0); HIPTRY(launch_ln_rows(tq, ns, m->gt, m->bet, cf.ln_eps, H, hq32, nullptr, hq16, kx, st)); }
-        int* lab = m->lab.as<int>();
-        float* ll = m->llog.as<float>();
-        { ProfScope ps(m, st, RS_K_OTHER, 0); HIPTRY(launch_gather_labels(d_tok, sm, c.s0, c.s1, lab, st)); }
-        ep = EpiArgs{}; ep.bias = m->bdec; ep.n_valid = cf.vocab; ep.lse_part = m->part.as<float2>();
-        ep.n_parts = m->vpad / 64; ep.label = lab; ep.label_logit = ll;
-        if (int r = gemm(m, st, RS_K_DECODER, EPI_LSE, hq16, m->wdec, ns, m->vpad, kx * H, ep, cf.vocab)) return r;
-        ProfScope ps(m, st, RS_K_OTHER, 0);
-        HIPTRY(launch_lse_finalize(m->part.as<float2>(), m->vpad / 64, ll, ns, d_out_rows + c.s0, st));
-    } else {
-        ProfScope ps(m, st, RS_K_OTHER, 0);
-        HIPTRY(launch_cls_linear(hq32, ns, H, m->wlin, m->blin, d_out_rows + c.s0, st));
+    // fp16x3 split-operand full layer
+    int layer_split(int li, bool uq) {
+        const Layer& L = m->layers[li];
+        LAUNCH(RS_K_ATTN, launch_attention_full(qkv, true, sm, c.s0, c.s1, 0, H, nh, ctx, 2, st, uq, c.max_len));
+        if (int r = split_block(RS_K_OPROJ, ctx, L.io, H, L.bo, prev_g(li), prev_b(li), L.g1, L.be1)) return r;
+        if (int r = gemm(RS_K_FFN1, EPI_GELU_F16, true, h16, L.i1, rows, F, H, gelu_ep(L.b1, inter, 2), F)) return r;
+        return split_block(RS_K_FFN2, inter, L.i2, F, L.b2, L.g1, L.be1, L.g2, L.be2);
     }
-    return RS_OK;
-}
+
+    // fp16 / K-concatenated fp16x3 full layer.  Each of its two residual blocks is a GEMM and a rows
+    // pass; which pair closes it is o.oproj_f16 / o.lnres_defer, then o.lnres_defer / o.ffn2_f16.
+    int layer_f16(int li, bool uq) {
+        const Layer& L = m->layers[li];
+        const float *pg = prev_g(li), *pb = prev_b(li);
+        LAUNCH(RS_K_ATTN, launch_attention_full(qkv, q32, sm, c.s0, c.s1, 0, H, nh, ctx, kx, st, uq, c.max_len));
+        // O-projection output (fp16): the dead QKV buffer when the BertOutput GEMM reads it
+        // back (deferred residual: it must survive FFN1), else the (free) FFN1 buffer
+        f16* o16 = o.lnres_defer ? (f16*)qkv : inter;
+        if (!o.oproj_f16) {
+            // residual rebuilt in the GEMM's accumulators, LayerNorm as a rows pass
+            if (int r = gemm(RS_K_OPROJ, EPI_RESLN_F32, false, ctx, L.wo, rows, H, kx * H, resln_ep(L.bo, pg, pb), H))
+                return r;
+            LAUNCH_OTHER(launch_ln_rows(t32, rows, L.g1, L.be1, eps, H, nullptr, xst, h16, kx, st));
+        } else {
+            // O projection as a persistent fp16-output GEMM; the residual add + LayerNorm
+            // move into ln_res_rows, off the GEMM's critical path
+            if (int r = gemm(RS_K_OPROJ, EPI_BIAS_F16, false, ctx, L.wo, rows, H, H, bias_ep(L.bo, o16, H), H)) return r;
+            if (o.lnres_defer)    // x = LN0(x32) + o1 is not written back: its statistics go to xst1
+                LAUNCH_OTHER(launch_ln_res_rows(t32, xst, xst1, pg, pb, o16, rows, L.g1, L.be1, eps, H, h16, false, st));
+            else
+                LAUNCH_OTHER(launch_ln_res_rows(t32, xst, xst, pg, pb, o16, rows, L.g1, L.be1, eps, H, h16, true, st));
+        }
+        if (int r = gemm(RS_K_FFN1, EPI_GELU_F16, false, h16, L.w1, rows, F, kx * H, gelu_ep(L.b1, inter, kx), F)) return r;
+        if (o.lnres_defer == 2) {
+            // BertOutput as a persistent fp16-output GEMM into the (free) ctx buffer; both
+            // residual blocks of the layer are closed by one ln_res_rows pass
+            if (int r = gemm(RS_K_FFN2, EPI_BIAS_F16, false, inter, L.w2, rows, H, F, bias_ep(L.b2, ctx, H), H)) return r;
+            LAUNCH_OTHER(launch_ln_res_rows(t32, xst, xst, pg, pb, o16, rows, L.g2, L.be2, eps, H, h16, true, st, xst1,
+                                            L.g1, L.be1, ctx));
+        } else if (o.ffn2_f16) {
+            // same split for BertOutput: fp16-output GEMM into the (free) ctx buffer
+            if (int r = gemm(RS_K_FFN2, EPI_BIAS_F16, false, inter, L.w2, rows, H, F, bias_ep(L.b2, ctx, H), H)) return r;
+            LAUNCH_OTHER(launch_ln_res_rows(t32, xst, xst, L.g1, L.be1, ctx, rows, L.g2, L.be2, eps, H, h16, true, st));
+        } else if (o.lnres_defer == 1) {
+            // the GEMM rebuilds the post-attention stream from (x32, o1) in its accumulator init
+            EpiArgs ep = resln_ep(L.b2, L.g1, L.be1);
+            ep.res_stats = xst1; ep.res_o16 = o16; ep.res_stats0 = xst; ep.res_g0 = pg; ep.res_b0 = pb;
+            if (int r = gemm(RS_K_FFN2, EPI_RESLN_F32, false, inter, L.w2, rows, H, kx * F, ep, H)) return r;
+            LAUNCH_OTHER(launch_ln_rows(t32, rows, L.g2, L.be2, eps, H, nullptr, xst, h16, kx, st));
+        } else {
+            if (int r = gemm(RS_K_FFN2, EPI_RESLN_F32, false, inter, L.w2, rows, H, kx * F, resln_ep(L.b2, L.g1, L.be1), H))
+                return r;
+            LAUNCH_OTHER(launch_ln_rows(t32, rows, L.g2, L.be2, eps, H, nullptr, xst, h16, kx, st));
+        }
+        return RS_OK;
+    }
+
+    // Last layer of the scoring modes: only the scored row of every sequence (one row per sequence)
+    int layer_query(int li, bool qrow) {
+        const Layer& L = m->layers[li];
+        LAUNCH(RS_K_ATTN, launch_attention_query(qkv, q32, t32, xst, prev_g(li), prev_b(li), sm, c.s0, c.s1, 0, H, nh,
+                                                 ctxq, resq, kx, st, qrow ? tq : nullptr, o.imgres ? h16 : nullptr));
+        if (int r = gemm(RS_K_OPROJ, EPI_RES_F32, false, ctxq, L.wo, ns, H, kx * H, bias_ep(L.bo, tq, H, resq), H))
+            return r;
+        LAUNCH_OTHER(launch_ln_rows(tq, ns, L.g1, L.be1, eps, H, hq32, nullptr, hq16, kx, st));
+        if (int r = gemm(RS_K_FFN1, EPI_GELU_F16, false, hq16, L.w1, ns, F, kx * H, gelu_ep(L.b1, interq, kx), F)) return r;
+        if (int r = gemm(RS_K_FFN2, EPI_RES_F32, false, interq, L.w2, ns, H, kx * F, bias_ep(L.b2, tq, H, hq32), H))
+            return r;
+        LAUNCH_OTHER(launch_ln_rows(tq, ns, L.g2, L.be2, eps, H, hq32, nullptr, hq16, kx, st));
+        return RS_OK;
+    }
+
+    int head_mlm(float* d_out_rows) {
+        if (int r = gemm(RS_K_DECODER, EPI_GELU_F32, false, hq16, m->wt, ns, H, kx * H, bias_ep(m->bt, tq, H), H)) return r;
+        LAUNCH_OTHER(launch_ln_rows(tq, ns, m->gt, m->bet, eps, H, hq32, nullptr, hq16, kx, st));
+        LAUNCH_OTHER(launch_gather_labels(d_tok, sm, c.s0, c.s1, m->lab.as<int>(), st));
+        EpiArgs ep{};
+        ep.bias = m->bdec; ep.n_valid = cf.vocab; ep.lse_part = m->part.as<float2>();
+        ep.n_parts = m->vpad / 64; ep.label = m->lab.as<int>(); ep.label_logit = m->llog.as<float>();
+        if (int r = gemm(RS_K_DECODER, EPI_LSE, false, hq16, m->wdec, ns, m->vpad, kx * H, ep, cf.vocab)) return r;
+        LAUNCH_OTHER(launch_lse_finalize(m->part.as<float2>(), m->vpad / 64, m->llog.as<float>(), ns, d_out_rows + c.s0,
+                                         st));
+        return RS_OK;
+    }
+    int head_cls(float* d_out_rows) {
+        LAUNCH_OTHER(launch_cls_linear(hq32, ns, H, m->wlin, m->blin, d_out_rows + c.s0, st));
+        return RS_OK;
+    }
+    int emb_out() {
+        LAUNCH_OTHER(launch_embed_out(t32, xst, prev_g(cf.layers), prev_b(cf.layers), sm, c.s0, c.s1, 0, H, m->emb_dst, st,
+                                      o.imgres ? h16 : nullptr, m->kx == 3));
+        return RS_OK;
+    }
+    // d_out_rows: one float per sequence of the call (MLM / CLS modes)
+    int run(float* d_out_rows) {
+        if (int r = embed()) return r;
+        for (int li = 0; li < cf.layers; ++li) {
+            const bool last = mode != MODE_EMB && li == cf.layers - 1;   // the scoring modes' last layer
+            const bool uq = dedup && li == 0;
+            const bool qrow = last && !uq && o.lastq;                     // query-row-only Q projection
+            if (int r = qkv_proj(li, last, uq, qrow)) return r;
+            if (int r = last ? layer_query(li, qrow) : o.x3s ? layer_split(li, uq) : layer_f16(li, uq)) return r;
+        }
+        if (mode == MODE_EMB) return emb_out();
+        return mode == MODE_MLM ? head_mlm(d_out_rows) : head_cls(d_out_rows);
+    }
+};
 
 // Host-side sequence list (structure of arrays) for one call.
 struct SeqList {
@@ -721,34 +736,30 @@ int plan_unique_rows(SeqList& sl, int s0, int s1) {
     return u;
 }
 
-// Chunks the sequence list, uploads metadata, runs every chunk.  out_rows: one float per
-// sequence.  Extra int arrays (e.g. hypothesis -> sequence offsets) ride in the same upload.
-int run_all(rs_model* m, hipStream_t st, const int* d_tok, SeqList& sl, int mode, float* out_rows,
-            const std::vector<int>* extra, int** d_extra, const int* d_label = nullptr) {
+int validate_call(const rs_model* m, int mode) {
     if (!m->finalized) return fail(RS_ESTATE, "rs_model_finalize not called");
     if (mode == MODE_MLM && !(m->cfg.heads_mask & RS_HEAD_MLM)) return fail(RS_ESTATE, "model has no MLM head");
     if (mode == MODE_CLS && !(m->cfg.heads_mask & RS_HEAD_CLS)) return fail(RS_ESTATE, "model has no CLS linear head");
-    if (m->max_rows == 0)
-        if (int r = reserve_impl(m, 65536)) return r;
-    HIPTRY(hipSetDevice(m->device));
-    if (int r = begin_call(m, st)) return r;
-    const size_t S = sl.size();
-    std::vector<Chunk> chunks;
-    // Chunk rows: with the fused residual + LayerNorm GEMMs (lnfuse), a chunk of P row panels runs
-    // ceil(P / G) rounds of whole panels on G = gemm_lnres_workgroups / (H / 256) gangs, so the
-    // chunks are cut at a multiple of 256 * G rows (bert-base on 256 CUs: 85 gangs, 21760 rows;
-    // 262144 -> 261120 rows = 12 full rounds instead of 12 + a 4-panel 13th).  RS_CHUNK_ALIGN=0
-    // keeps max_rows (read per call).
+    return RS_OK;
+}
+
+// Chunk rows: with the fused residual + LayerNorm GEMMs (lnfuse), a chunk of P row panels runs
+// ceil(P / G) rounds of whole panels on G = gemm_lnres_workgroups / (H / 256) gangs, so the
+// chunks are cut at a multiple of 256 * G rows (bert-base on 256 CUs: 85 gangs, 21760 rows;
+// 262144 -> 261120 rows = 12 full rounds instead of 12 + a 4-panel 13th); RS_CHUNK_ALIGN=0: max_rows.
+int64_t chunk_cap(const rs_model* m, const CallOpts& o) {
     int64_t cap = m->max_rows;
-    {
-        const char* ca = getenv("RS_CHUNK_ALIGN");
-        const bool lnf = m->kx == 3 && x3s_on(m) && x3s_imgres_on() && lnfuse_on(m->cfg);
-        const int ntn = m->cfg.hidden / 256;
-        if (lnf && !(ca && !strcmp(ca, "0")) && ntn > 0) {
-            const int64_t unit = (int64_t)256 * (gemm_lnres_workgroups(m->cfg.hidden) / ntn);
-            if (unit > 0 && cap >= unit) cap = cap / unit * unit;
-        }
+    const int ntn = m->cfg.hidden / 256;
+    if (o.lnfuse && o.chunk_align && ntn > 0) {
+        const int64_t unit = (int64_t)256 * (gemm_lnres_workgroups(m->cfg.hidden) / ntn);
+        if (unit > 0 && cap >= unit) cap = cap / unit * unit;
     }
+    return cap;
+}
+
+// Chunks of <= cap rows and <= s_cap sequences; sets sl.row (first row of a sequence in its chunk).
+int cut_chunks(const rs_model* m, SeqList& sl, int64_t cap, std::vector<Chunk>* chunks) {
+    const size_t S = sl.size();
     int rows = 0, s0 = 0, max_len = 0;
     for (size_t s = 0; s < S; ++s) {
         const int T = sl.len[s];
@@ -756,7 +767,7 @@ int run_all(rs_model* m, hipStream_t st, const int* d_tok, SeqList& sl, int mode
         if (T < 1) return fail(RS_EARG, "empty sequence");
         if (T > m->max_rows) return fail(RS_EARG, "sequence longer than the reserved rows");
         if (rows + T > cap || (int)s - s0 >= m->s_cap) {
-            chunks.push_back({s0, (int)s, rows, 0, max_len});
+            chunks->push_back({s0, (int)s, rows, 0, max_len});
             s0 = (int)s;
             rows = 0;
             max_len = 0;
@@ -765,43 +776,55 @@ int run_all(rs_model* m, hipStream_t st, const int* d_tok, SeqList& sl, int mode
         rows += T;
         max_len = std::max(max_len, T);
     }
-    if (S) chunks.push_back({s0, (int)S, rows, 0, max_len});
-    // layer-0 dedup: MLM mode, fp16 operands, >= 2 layers (layer 0 is not the query-only layer)
-    const char* dedup_s = getenv("RS_DEDUP");      // read per call (tests flip it)
-    const int dedup_env = dedup_s ? atoi(dedup_s) : 1;
-    // fp16x3: the split-operand layer with the image-held residual (its attention kernel reads
-    // the unique rows for chunks with T <= 64)
-    const bool x3_dedup = m->kx == 3 && x3s_on(m) && x3s_imgres_on();
-    if (dedup_env && mode == MODE_MLM && (m->kx == 1 || x3_dedup) && m->cfg.layers >= 2)
-        for (Chunk& c : chunks)
-            if (m->kx == 1 || c.max_len <= 64) c.urows = plan_unique_rows(sl, c.s0, c.s1);
+    if (S) chunks->push_back({s0, (int)S, rows, 0, max_len});
+    return RS_OK;
+}
 
-    // one upload of all metadata through a pinned staging buffer
-    const size_t n_extra = extra ? extra->size() : 0;
-    const size_t n_int = 8 * S + n_extra;
-    if (m->upload_done) HIPTRY(hipEventSynchronize(m->upload_done));
-    if (n_int > m->pinned_cap) {
-        if (m->pinned) (void)hipHostFree(m->pinned);
-        m->pinned = nullptr;
-        m->pinned_cap = 0;
-        HIPTRY(hipHostMalloc((void**)&m->pinned, std::max<size_t>(n_int, 1) * 4, hipHostMallocDefault));
-        m->pinned_cap = n_int;
-    }
-    int* p = m->pinned;
+// Layer-0 dedup plan (plan_unique_rows) of every chunk it applies to (call_opts: RS_DEDUP, x3_dedup).
+void plan_dedup(const rs_model* m, const CallOpts& o, int mode, SeqList& sl, std::vector<Chunk>& chunks) {
+    if (!(o.dedup && mode == MODE_MLM && (m->kx == 1 || o.x3_dedup) && m->cfg.layers >= 2)) return;
+    for (Chunk& c : chunks)
+        if (m->kx == 1 || c.max_len <= 64) c.urows = plan_unique_rows(sl, c.s0, c.s1);
+}
+
+// One upload of all metadata through the pinned staging buffer: the eight SeqList columns, then
+// the extra ints (e.g. hypothesis -> sequence offsets; *d_extra); d_label: device labels instead.
+int upload_meta(rs_model* m, hipStream_t st, const SeqList& sl, const std::vector<int>* extra, const int* d_label,
+                SeqMeta* sm, int** d_extra) {
+    const size_t S = sl.size(), n_extra = extra ? extra->size() : 0, n_int = 8 * S + n_extra;
+    HIPTRY(m->stage_meta.begin(n_int));
+    int* p = m->stage_meta.p;
     const std::vector<int>* cols[8] = {&sl.tok_off, &sl.len, &sl.mask, &sl.query, &sl.label, &sl.row,
                                        &sl.urow_h, &sl.urow_m};
     for (int k = 0; k < 8; ++k) std::memcpy(p + k * S, cols[k]->data(), S * 4);
     if (n_extra) std::memcpy(p + 8 * S, extra->data(), n_extra * 4);
-    HIPTRY(m->meta.ensure(std::max<size_t>(n_int, 1) * 4));
-    HIPTRY(hipMemcpyAsync(m->meta.p, p, n_int * 4, hipMemcpyHostToDevice, st));
-    if (!m->upload_done) HIPTRY(hipEventCreateWithFlags(&m->upload_done, hipEventDisableTiming));
-    HIPTRY(hipEventRecord(m->upload_done, st));
+    HIPTRY(m->stage_meta.upload(m->meta, n_int, st));
     int* d = m->meta.as<int>();
     if (d_label) HIPTRY(hipMemcpyAsync(d + 4 * S, d_label, S * 4, hipMemcpyDeviceToDevice, st));
-    SeqMeta sm{d, d + S, d + 2 * S, d + 3 * S, d + 4 * S, d + 5 * S, d + 6 * S, d + 7 * S};
+    *sm = SeqMeta{d, d + S, d + 2 * S, d + 3 * S, d + 4 * S, d + 5 * S, d + 6 * S, d + 7 * S};
     if (d_extra) *d_extra = d + 8 * S;
-    for (const Chunk& c : chunks)
-        if (int r = run_chunk(m, st, d_tok, sm, c, mode, out_rows)) return r;
+    return RS_OK;
+}
+
+// Chunks the sequence list, uploads metadata, runs every chunk.  out_rows: one float per
+// sequence.  Extra int arrays (e.g. hypothesis -> sequence offsets) ride in the same upload.
+int run_all(rs_model* m, hipStream_t st, const int* d_tok, SeqList& sl, int mode, float* out_rows,
+            const std::vector<int>* extra, int** d_extra, const int* d_label = nullptr) {
+    const CallOpts opts = call_opts(m);
+    if (int r = validate_call(m, mode)) return r;
+    if (m->max_rows == 0)
+        if (int r = reserve_impl(m, 65536)) return r;
+    HIPTRY(hipSetDevice(m->device));
+    if (int r = begin_call(m, st)) return r;
+    std::vector<Chunk> chunks;
+    if (int r = cut_chunks(m, sl, chunk_cap(m, opts), &chunks)) return r;
+    plan_dedup(m, opts, mode, sl, chunks);
+    SeqMeta sm{};
+    if (int r = upload_meta(m, st, sl, extra, d_label, &sm, d_extra)) return r;
+    for (const Chunk& c : chunks) {
+        ChunkCtx cx{m, st, d_tok, sm, c, opts, mode};
+        if (int r = cx.run(out_rows)) return r;
+    }
     return RS_OK;
 }
 
@@ -1005,7 +1028,6 @@ int rs_pll_score(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off, in
     if (!m || !h_hyp_off || n_hyp < 0 || (n_hyp > 0 && (!d_tok || !d_pll))) return fail(RS_EARG, "null argument");
     hipStream_t st = (hipStream_t)stream;
     if (n_hyp == 0) return RS_OK;
-    HIPTRY(hipSetDevice(m->device));
     CALL_ORDER(m, st);
     SeqList sl;
     std::vector<int> hso(n_hyp + 1, 0);
@@ -1022,10 +1044,7 @@ int rs_pll_score(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off, in
     }
     int* d_hso = nullptr;
     if (int r = run_all(m, st, d_tok, sl, MODE_MLM, rows, &hso, &d_hso)) return r;
-    {
-        ProfScope ps(m, st, RS_K_OTHER, 0);
-        HIPTRY(launch_segsum_f64(rows, d_hso, n_hyp, d_pll, st));
-    }
+    LAUNCH_OTHER(launch_segsum_f64(rows, d_hso, n_hyp, d_pll, st));
     return check_finite(m, st, rows, sl.size(), "masked-token log-probability");
 }
 
@@ -1035,7 +1054,6 @@ int rs_masked_logprob(rs_model* m, const int32_t* d_ids, const int32_t* h_seq_of
     if (!m || !h_seq_off || !h_query || n_seq < 0 || (n_seq > 0 && (!d_ids || !d_label || !d_out)))
         return fail(RS_EARG, "null argument");
     if (n_seq == 0) return RS_OK;
-    HIPTRY(hipSetDevice(m->device));
     CALL_ORDER(m, (hipStream_t)stream);
     SeqList sl;
     for (int s = 0; s < n_seq; ++s) {
@@ -1051,7 +1069,6 @@ int rs_cls_score(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off, in
                  float* d_out, void* stream) {
     if (!m || !h_hyp_off || n_hyp < 0 || (n_hyp > 0 && (!d_tok || !d_out))) return fail(RS_EARG, "null argument");
     if (n_hyp == 0) return RS_OK;
-    HIPTRY(hipSetDevice(m->device));
     CALL_ORDER(m, (hipStream_t)stream);
     SeqList sl;
     for (int h = 0; h < n_hyp; ++h) {
@@ -1067,7 +1084,6 @@ int rs_token_embed(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off, 
                    void* d_emb, void* stream) {
     if (!m || !h_hyp_off || n_hyp < 0 || (n_hyp > 0 && (!d_tok || !d_emb))) return fail(RS_EARG, "null argument");
     if (n_hyp == 0) return RS_OK;
-    HIPTRY(hipSetDevice(m->device));
     CALL_ORDER(m, (hipStream_t)stream);
     SeqList sl;
     for (int h = 0; h < n_hyp; ++h) {
@@ -1099,7 +1115,6 @@ int rs_bertscore_recall(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_
         if (h_hyp_off[h + 1] - h_hyp_off[h] < 2)
             return fail(RS_EARG, "hypothesis " + std::to_string(h) + " has fewer than 2 tokens ([CLS] [SEP])");
     hipStream_t st = (hipStream_t)stream;
-    HIPTRY(hipSetDevice(m->device));
     CALL_ORDER(m, st);
     const int H = m->cfg.hidden;
     const size_t n_tok = (size_t)h_hyp_off[n_hyp];
@@ -1127,27 +1142,17 @@ int rs_bertscore_recall(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_
     // one upload: items | mat_off (int64) | hyp_off | utt_off
     const size_t w_items = items.size(), w_moff = 2 * (size_t)(n_utt + 1);
     const size_t n_int = w_items + w_moff + (size_t)(n_hyp + 1) + (size_t)(n_utt + 1);
-    if (m->plan_done) HIPTRY(hipEventSynchronize(m->plan_done));
-    if (n_int > m->pinned_plan_cap) {
-        if (m->pinned_plan) (void)hipHostFree(m->pinned_plan);
-        m->pinned_plan = nullptr;
-        m->pinned_plan_cap = 0;
-        HIPTRY(hipHostMalloc((void**)&m->pinned_plan, n_int * 4, hipHostMallocDefault));
-        m->pinned_plan_cap = n_int;
-    }
-    int* p = m->pinned_plan;
+    HIPTRY(m->stage_plan.begin(n_int));
+    int* p = m->stage_plan.p;
     std::memcpy(p, items.data(), w_items * 4);
     std::memcpy(p + w_items, moff.data(), w_moff * 4);
     std::memcpy(p + w_items + w_moff, h_hyp_off, (size_t)(n_hyp + 1) * 4);
     std::memcpy(p + w_items + w_moff + n_hyp + 1, h_utt_off, (size_t)(n_utt + 1) * 4);
-    HIPTRY(m->plan.ensure(n_int * 4));
-    HIPTRY(hipMemcpyAsync(m->plan.p, p, n_int * 4, hipMemcpyHostToDevice, st));
-    if (!m->plan_done) HIPTRY(hipEventCreateWithFlags(&m->plan_done, hipEventDisableTiming));
-    HIPTRY(hipEventRecord(m->plan_done, st));
+    HIPTRY(m->stage_plan.upload(m->plan, n_int, st));
     int* d = m->plan.as<int>();
-    ProfScope ps(m, st, RS_K_OTHER, 0);
-    HIPTRY(launch_bertscore_recall(m->emb.as<f16>(), H, d + w_items + w_moff, d + w_items + w_moff + n_hyp + 1,
-                                   (const long long*)(d + w_items), (const int4*)d, n_items, d_rmat, d_rmat0, st, two));
+    LAUNCH_OTHER(launch_bertscore_recall(m->emb.as<f16>(), H, d + w_items + w_moff, d + w_items + w_moff + n_hyp + 1,
+                                         (const long long*)(d + w_items), (const int4*)d, n_items, d_rmat, d_rmat0, st,
+                                         two));
     return RS_OK;
 }
 
@@ -1159,7 +1164,6 @@ int rs_model_set_sync_check(rs_model* m, int on) {
 
 int rs_check(rs_model* m, void* stream) {
     if (!m) return fail(RS_EARG, "null model");
-    HIPTRY(hipSetDevice(m->device));
     CALL_ORDER(m, (hipStream_t)stream);
     return report_flags(m, (hipStream_t)stream, "scores");
 }
@@ -1188,14 +1192,10 @@ void rs_model_destroy(rs_model* m) {
     for (void* p : m->allocs) (void)hipFree(p);
     for (DevBuf* b : {&m->xst, &m->xst1, &m->h16, &m->t32, &m->qkv, &m->ctx, &m->inter, &m->ctxq, &m->resq,
                       &m->tq32, &m->hq32, &m->hq16, &m->interq, &m->lab, &m->llog, &m->part,
-                      &m->rowlp_tmp, &m->meta, &m->hypoff, &m->emb, &m->plan, &m->flag, &m->lnx, &m->lncnt,
+                      &m->rowlp_tmp, &m->meta, &m->emb, &m->plan, &m->flag, &m->lnx, &m->lncnt,
                       &m->lnerr})
         b->release();
-    if (m->pinned) (void)hipHostFree(m->pinned);
-    if (m->pinned_plan) (void)hipHostFree(m->pinned_plan);
     if (m->pinned_flag) (void)hipHostFree(m->pinned_flag);
-    if (m->plan_done) (void)hipEventDestroy(m->plan_done);
-    if (m->upload_done) (void)hipEventDestroy(m->upload_done);
     if (m->call_done) (void)hipEventDestroy(m->call_done);
     for (hipEvent_t e : m->ev_pool) (void)hipEventDestroy(e);
     delete m;

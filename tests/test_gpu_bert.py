@@ -99,24 +99,36 @@ def test_pll_tiny_golden(pll_tiny, golden_dir):
     assert rel_err(rows.cpu().numpy(), g["row_lp"]).max() < REL
 
 
-@pytest.mark.parametrize("x3s,lnfuse", [("1", "1"), ("1", "0"), ("0", "1")])
-def test_pll_fp16x3_golden(w_base, golden_dir, monkeypatch, x3s, lnfuse):
+@pytest.mark.parametrize("x3s,lnfuse,imgres", [("1", "1", "1"), ("1", "0", "1"), ("0", "1", "1"), ("1", "1", "0")],
+                         ids=["1-1", "1-0", "0-1", "1-1-imgres0"])
+def test_pll_fp16x3_golden(w_base, golden_dir, monkeypatch, x3s, lnfuse, imgres):
     """Split-fp16 (x3) precision mode: fp32-level accuracy from fp16 MFMA, with the split-operand
     GEMMs (RS_X3S=1, default: two-part images, three products in registers) and with the
     K-concatenated three-part form (RS_X3S=0); split-operand layers with the residual +
-    LayerNorm in the O-projection / BertOutput epilogues (RS_LNFUSE=1, default) and as separate
-    ln_res_img passes (RS_LNFUSE=0)."""
+    LayerNorm in the O-projection / BertOutput epilogues (RS_LNFUSE=1, default), as separate
+    ln_res_img passes (RS_LNFUSE=0), and with the residual held as the fp32 pre-LN stream closed by
+    ln_res32 (RS_X3S_IMGRES=0, where RS_LNFUSE has no effect: eleven ln_res32 layers)."""
     from asr_rescoring_amd.scorer import PLLScorer
-    monkeypatch.setenv("RS_X3S", x3s)
-    monkeypatch.setenv("RS_LNFUSE", lnfuse)
     g = _load(golden_dir, "pll_base.npz")
     s = PLLScorer(w_base, BERT_BASE, device=0, max_rows=4096, precision="fp16x3")
-    pll, rows = s.score_nbest(g["tokens"], g["hyp_off"], return_rows=True)
-    s.close()
+    try:
+        default = s.score_nbest(g["tokens"], g["hyp_off"]).cpu().numpy() if imgres == "0" else None
+        monkeypatch.setenv("RS_X3S", x3s)
+        monkeypatch.setenv("RS_LNFUSE", lnfuse)
+        monkeypatch.setenv("RS_X3S_IMGRES", imgres)
+        pll, rows = s.score_nbest(g["tokens"], g["hyp_off"], return_rows=True)
+    finally:
+        s.close()
+    e_pll = rel_err(pll.cpu().numpy(), g["pll"]).max()
+    e_rows = rel_err(rows.cpu().numpy(), g["row_lp"]).max()
+    print(f"fp16x3 golden x3s={x3s} lnfuse={lnfuse} imgres={imgres}: pll {e_pll:.3e} rows {e_rows:.3e}")
     # measured 1.9e-7 (PLL) / 1.1e-6 (rows) with the lo parts scaled out of the fp16 subnormal
     # range (common.h put_split); 2e-5 / 2e-5 before, when the f16 MFMA flushed them
-    assert rel_err(pll.cpu().numpy(), g["pll"]).max() < 1e-6
-    assert rel_err(rows.cpu().numpy(), g["row_lp"]).max() < 5e-6
+    # (RS_X3S_IMGRES=0: 1.2e-7 / 1.3e-6)
+    assert e_pll < 1e-6
+    assert e_rows < 5e-6
+    if default is not None:
+        assert not np.array_equal(pll.cpu().numpy(), default)     # the switch really took effect
 
 
 @pytest.mark.parametrize("max_rows", [4096, 65536, 262144])
@@ -287,6 +299,28 @@ def test_layer0_dedup_is_exact(w_tiny, w_base, max_rows, prec, monkeypatch):
             b = s.score(nb)
         finally:
             s.close()
+        assert np.array_equal(a, b), np.abs(a - b).max()
+
+
+@pytest.mark.parametrize("prec", ["fp16", "fp16x3"])
+@pytest.mark.parametrize("max_rows", [512, 65536])
+def test_lastq_full_layer_is_exact(w_tiny, w_base, max_rows, prec, monkeypatch):
+    """Query-row-only last layer (default) vs the full Q/K/V GEMM at the last layer (RS_LASTQ=0):
+    the scored row's Q goes through the same GEMM on the same operand row either way, so scores
+    are bitwise equal (INTEGRATION.md).  BERT_TINY: layer 0 full, layer 1 the query layer;
+    max_rows=512 gives several chunks whose sequence count is no multiple of the row alignment."""
+    from asr_rescoring_amd.scorer import PLLScorer
+    for w, cfg, seed in ((w_tiny, BERT_TINY, 5), (w_base, BERT_BASE, 6)):
+        nb = D.synthetic_nbest(5, 4, seed=seed, vocab=cfg.vocab, len_lo=1, len_hi=70)
+        s = PLLScorer(w, cfg, device=0, max_rows=max_rows, precision=prec)
+        try:
+            monkeypatch.delenv("RS_LASTQ", raising=False)
+            a = s.score(nb)
+            monkeypatch.setenv("RS_LASTQ", "0")
+            b = s.score(nb)
+        finally:
+            s.close()
+        print(f"lastq {cfg.layers} layers {prec} max_rows={max_rows}: max rel diff {rel_err(b, a).max():.3e}")
         assert np.array_equal(a, b), np.abs(a - b).max()
 
 
