@@ -116,7 +116,22 @@ _DEBUG_SIGS = {
     "rs_debug_lnres_sizes": (CI, [CI, CI, ctypes.POINTER(I64)]),
     # (qkv32, len, row, n_seq, max_len, H, heads, kx, ctx, stream)
     "rs_debug_attention_full": (CI, [P, P, P, CI, CI, CI, CI, CI, P, P]),
+    # (epi, A, W, M_pad, N_pad, K, DebugGemmEpi*, stream)
+    "rs_debug_gemm_epi": (CI, [CI, P, P, CI, CI, CI, P, P]),
+    # (A, W, bias, label, M_pad, m_valid, vpad, vocab, K, lab, part, llog, out, stream)
+    "rs_debug_decoder": (CI, [P, P, P, P, CI, CI, CI, CI, CI, P, P, P, P, P]),
+    # (qkv, qkv32, len, row, query, s0, s1, row0, H, heads, kx, qd, x32, stats, g, b, himg, ctxq, resq, stream)
+    "rs_debug_attention_query": (CI, [P, CI, P, P, P, CI, CI, CI, CI, CI, CI, P, P, P, P, P, P, P, P, P]),
 }
+
+
+class DebugGemmEpi(ctypes.Structure):
+    """The EpiArgs fields rs_debug_gemm_epi takes (csrc/k_gemm.hip DebugGemmEpi)."""
+    _fields_ = [(n, P) for n in ("bias", "res", "res_stats", "res_g", "res_b", "out", "res_o16", "res_stats0",
+                                 "res_g0", "res_b0")] + [(n, CI) for n in ("ldc", "m_valid", "kx", "nlog")]
+
+
+
 EXPORTED = tuple(_SIGS)          # the shipped library's entries (include/rescore.h)
 _SIGS.update(_DEBUG_SIGS)
 

@@ -229,10 +229,47 @@ hipError_t launch_attention_query(const void* qkv, bool qkv32, const float* x32,
 // dst[s - s0] = src[row of sequence s's query position], ld halfs per row
 hipError_t launch_gather_query_rows(const f16* src, int ld, SeqMeta sm, int s0, int s1, int row0, f16* dst,
                                    hipStream_t st);
-hipError_t launch_gather_labels(const int* tok, SeqMeta sm, int s0, int s1, int* lab,
+// lab[s - s0] = the label column of sequence s (SeqMeta.label, -1 = the token at its query
+// position; tok == null: SeqMeta.label as given), and label_logit[s - s0] = -inf: the EPI_LSE
+// epilogue stores a row's label logit only where a valid column equals the label, so a label
+// outside [0, vocab) leaves -inf, a -inf log-prob, and the call's range guard reports it
+hipError_t launch_gather_labels(const int* tok, SeqMeta sm, int s0, int s1, int* lab, float* label_logit,
                                 hipStream_t st);
 hipError_t launch_lse_finalize(const float2* part, int n_parts, const float* label_logit,
                                int rows, float* out, hipStream_t st);
+
+// The MLM decoder over one state row per sequence of [s0, s0 + m_valid): out[i] =
+// log_softmax(A[i] . W^T + bias)[label of sequence s0 + i] over the first `vocab` of vpad columns.
+// Three launches: the labels (and the label logits' -inf), the EPI_LSE GEMM into part / llog, the
+// merge of the 64-column slabs.  A [pad(m_valid, 256), K], W [vpad, K] fp16 operand images,
+// vpad % 128 == 0; lab / llog [m_valid], part [m_valid, vpad / 64]: the caller's workspace.
+struct MlmDecoder {
+    const f16* A;
+    const f16* W;
+    const float* bias;     // [vpad]
+    int m_valid, vpad, vocab, K;
+    const int* tok;        // as launch_gather_labels takes them
+    SeqMeta sm;
+    int s0;
+    int* lab;
+    float2* part;
+    float* llog;
+    float* out;            // [m_valid]
+};
+// wrap(is_gemm, launch) runs one launch and returns its error: the scorer's profiler scopes
+// (rs_api.hip head_mlm), or a plain call (the rs_debug_decoder test entry)
+template <class Wrap>
+hipError_t launch_mlm_decoder(const MlmDecoder& d, hipStream_t st, Wrap&& wrap) {
+    if (hipError_t e = wrap(false, [&] { return launch_gather_labels(d.tok, d.sm, d.s0, d.s0 + d.m_valid, d.lab, d.llog, st); }))
+        return e;
+    EpiArgs ep{};
+    ep.bias = d.bias; ep.m_valid = d.m_valid; ep.n_valid = d.vocab; ep.lse_part = d.part;
+    ep.n_parts = d.vpad / 64; ep.label = d.lab; ep.label_logit = d.llog;
+    const int al = gemm_row_align(), m_pad = (d.m_valid + al - 1) / al * al;
+    if (hipError_t e = wrap(true, [&] { return launch_gemm(EPI_LSE, d.A, d.W, m_pad, d.vpad, d.K, ep, st, 0); }))
+        return e;
+    return wrap(false, [&] { return launch_lse_finalize(d.part, d.vpad / 64, d.llog, d.m_valid, d.out, st); });
+}
 hipError_t launch_cls_linear(const float* h, int rows, int H, const float* w, const float* b,
                              float* out, hipStream_t st);
 hipError_t launch_segsum_f64(const float* row_lp, const int* hyp_seq_off, int n_hyp, double* out,

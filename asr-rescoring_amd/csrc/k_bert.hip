@@ -900,13 +900,17 @@ gather_query_rows_kernel(const f16* __restrict__ src, int ld, SeqMeta sm, int s0
     for (int i = threadIdx.x; i < ld / 8; i += 64) o[i] = a[i];
 }
 
+// The label may be any int (a caller's label, or a raw token id: the embedding clamps ids, the
+// label is not clamped): the decoder epilogue only compares it with column indices, so one outside
+// [0, vocab) matches no column and the row keeps the -inf written here.
 __global__ void gather_labels_kernel(const int* __restrict__ tok, SeqMeta sm, int s0, int n,
-                                     int* __restrict__ lab) {
+                                     int* __restrict__ lab, float* __restrict__ label_logit) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int s = s0 + i;
     const int l = sm.label[s];
-    lab[i] = l >= 0 ? l : tok[sm.tok_off[s] + sm.query[s]];
+    lab[i] = (l == -1 && tok) ? tok[sm.tok_off[s] + sm.query[s]] : l;
+    label_logit[i] = -INFINITY;
 }
 
 __global__ void __launch_bounds__(256)
@@ -1201,10 +1205,11 @@ hipError_t launch_gather_query_rows(const f16* src, int ld, SeqMeta sm, int s0, 
     return hipGetLastError();
 }
 
-hipError_t launch_gather_labels(const int* tok, SeqMeta sm, int s0, int s1, int* lab, hipStream_t st) {
+hipError_t launch_gather_labels(const int* tok, SeqMeta sm, int s0, int s1, int* lab, float* label_logit,
+                                hipStream_t st) {
     const int n = s1 - s0;
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(gather_labels_kernel, dim3((n + 255) / 256), dim3(256), 0, st, tok, sm, s0, n, lab);
+    hipLaunchKernelGGL(gather_labels_kernel, dim3((n + 255) / 256), dim3(256), 0, st, tok, sm, s0, n, lab, label_logit);
     return hipGetLastError();
 }
 
@@ -1295,6 +1300,47 @@ extern "C" int rs_debug_attention_full(const void* qkv32, const int* len, const 
     sm.row = row;
     const hipError_t e = launch_attention_full(qkv32, true, sm, 0, n_seq, 0, H, heads, (f16*)ctx, kx,
                                                (hipStream_t)stream, false, max_len);
+    return e == hipSuccess ? 0 : -2;
+}
+
+// Test entry (not part of the scoring path): the last layer's scored-row attention through the
+// production launcher, over sequences [s0, s1) of the device metadata arrays len / row / query
+// (each [>= s1]).  qkv [rows, 3H] fp32 (qkv32 != 0) or fp16, row index = row[s] - row0 + t; qd null or
+// the dense Q [s1 - s0, H] of the same type; the residual from (x32 [rows, H], stats [rows], g, b
+// [H]) or, himg != null, from the interleaved two-part image [rows, 2H]; ctxq the kx = 1 or 3 image
+// [s1 - s0, kx H], resq fp32 [s1 - s0, H].
+extern "C" int rs_debug_attention_query(const void* qkv, int qkv32, const int* len, const int* row, const int* query,
+                                        int s0, int s1, int row0, int H, int heads, int kx, const void* qd,
+                                        const float* x32, const void* stats, const float* g, const float* b,
+                                        const void* himg, void* ctxq, float* resq, void* stream) {
+    if (!qkv || !len || !row || !query || !ctxq || !resq || s0 < 0 || s1 <= s0 || heads <= 0 || H != heads * 64) return -1;
+    if (kx != 1 && kx != 3) return -1;
+    if (!himg && (!x32 || !stats || !g || !b)) return -1;
+    SeqMeta sm{};
+    sm.len = len;
+    sm.row = row;
+    sm.query = query;
+    const hipError_t e = launch_attention_query(qkv, qkv32 != 0, x32, (const float2*)stats, g, b, sm, s0, s1, row0, H, heads,
+                                                (f16*)ctxq, resq, kx, (hipStream_t)stream, qd, (const f16*)himg);
+    return e == hipSuccess ? 0 : -2;
+}
+
+// Test entry (not part of the scoring path): the MLM decoder as rs_api.hip's head_mlm runs it
+// (launch_mlm_decoder: labels and label-logit preset, EPI_LSE GEMM, lse_finalize) with device labels
+// given as they are (any int: one outside [0, vocab) yields -inf).  A [M_pad, K], W [vpad, K] fp16,
+// bias [vpad], label [m_valid]; the caller's lab [m_valid] (int), part [M_pad, vpad / 64] (float2),
+// llog [M_pad], out [m_valid].
+extern "C" int rs_debug_decoder(const void* A, const void* W, const float* bias, const int* label, int M_pad, int m_valid,
+                                int vpad, int vocab, int K, int* lab, void* part, float* llog, float* out, void* stream) {
+    if (!A || !W || !bias || !label || !lab || !part || !llog || !out) return -1;
+    if (m_valid <= 0 || M_pad != (m_valid + 255) / 256 * 256 || vpad <= 0 || vpad % 128 || vocab <= 0 || vocab > vpad ||
+        K <= 0 || K % 64)
+        return -1;
+    SeqMeta sm{};
+    sm.label = label;
+    const MlmDecoder d{(const f16*)A, (const f16*)W, bias, m_valid, vpad, vocab, K, nullptr, sm, 0, lab,
+                       (float2*)part, llog, out};
+    const hipError_t e = launch_mlm_decoder(d, (hipStream_t)stream, [](bool, auto&& launch) { return launch(); });
     return e == hipSuccess ? 0 : -2;
 }
 

@@ -158,7 +158,7 @@ gemm_f16_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
         }
     };
 
-    // Accumulators start at bias (+ residual): these loads' latency hides behind the whole
+    // Accumulators start at bias (+ residual; EPI_LSE: at 0, below): these loads' latency hides behind the whole
     // K loop and the epilogue only converts / activates / stores.
     //   acc[i][j][4g + e] <-> C[m0 + wm*WTM + MS*i + (lane%MS)][n0 + wn*WTN + MS*j + qcol(g) + e]
     accT acc[TM][TN];
@@ -179,7 +179,11 @@ gemm_f16_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
 #pragma unroll
             for (int g = 0; g < NQ; ++g) {
                 const int col = acol + MS * j + qcol<MS>(g, lane);
-                const float4 b4 = *(const float4*)(ep.bias + col);
+                // EPI_LSE: the accumulators start at 0 and the bias is added after the K loop.  A
+                // decoder bias can be far larger than the products (a logit offset of 200): started at
+                // the bias, every one of the K / 16 MFMA steps rounds at its magnitude, and the
+                // log-prob loses |b| sqrt(K) 2^-24 (tests/test_gpu_gemm_epi.py, slab_spread)
+                const float4 b4 = EPI == EPI_LSE ? make_float4(0.f, 0.f, 0.f, 0.f) : *(const float4*)(ep.bias + col);
                 float4 lg4, lb4, lg04, lb04;
                 if constexpr (EPI == EPI_RESLN_F32) {
                     lg4 = *(const float4*)(ep.res_g + col);
@@ -300,6 +304,11 @@ gemm_f16_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
         static_assert(WTN == 64, "decoder logsumexp parts are 64-column slabs (n_parts = N/64)");
         // per (row, 64-column wave slab): max and sum exp over the slab + label logit
         const int slab = (n0 + wn * WTN) / WTN;
+        float4 bz[TN][4];                      // the bias of this lane's columns (added here, see above)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) bz[j][g] = *(const float4*)(ep.bias + cbase + j * 32 + 8 * g);
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
             const int row = rbase + i * 32;
@@ -311,10 +320,10 @@ gemm_f16_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const int col = cbase + j * 32 + 8 * g;
-
+                    const float b4[4] = {bz[j][g].x, bz[j][g].y, bz[j][g].z, bz[j][g].w};
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        const float x = col + e < ep.n_valid ? acc[i][j][4 * g + e] : -INFINITY;
+                        const float x = col + e < ep.n_valid ? acc[i][j][4 * g + e] + b4[e] : -INFINITY;
                         v[j][4 * g + e] = x;
                         mx = fmaxf(mx, x);
                         if (col + e == lab) ep.label_logit[row] = x;
@@ -409,8 +418,9 @@ gemm_f16_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
 // Per tile transition: barrier -> the NEXT tile's stage 0 (buffer 0) and bias are issued ->
 // this tile's epilogue (bias/GELU applied in registers, fp16, transposed through a per-wave
 // slab in buffer 1, whole 128-B row segments stored non-temporally).  The next tile then
-// waits vmcnt(NSTORE): its stage 0 and bias, not the stores (the stores are unconditional,
-// rows < M_pad are all allocated, so NSTORE is exact).  The bias loads are inline asm so the
+// waits vmcnt(NSTORE): its stage 0 and bias, not the stores (the stores of a row panel below
+// m_valid are unconditional, so NSTORE is exact; the last panel, which skips the rows >= m_valid,
+// drains its stores and the next tile's loads together).  The bias loads are inline asm so the
 // compiler's own (loop-merged, conservative) wait does not drain the stores; the wait asm
 // takes the bias registers as operands, so nothing reads them before it.
 // OPT: P_SCHED (the production wave schedule; without it the plain barrier-synchronised schedule,
@@ -657,6 +667,10 @@ gemm_persist_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K,
         const int rr0 = lane >> 3, cc = (lane & 7) * 8;
         uint4 ov[WTM / 32][4];
         f16* obase = (f16*)ep.out + (size_t)(cm0 + wm * WTM + rr0) * ep.ldc + cn0 + wn * WTN + cc;
+        // rows >= m_valid are not stored: a row panel below m_valid (all but the last one) keeps
+        // the unconditional stores; in the last panel this lane stores its rows r < vrows
+        const bool full = __builtin_expect(__builtin_amdgcn_readfirstlane(cm0 + BM <= ep.m_valid), 1);
+        const int row_lane = cm0 + wm * WTM + rr0;
         {
             // 32x32x16 accumulators: v_permlane32_swap packs 8 consecutive columns per lane
             // (lanes 0-31 the low, 32-63 the high 8 of each 16-column pair), stored as one
@@ -724,7 +738,8 @@ gemm_persist_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K,
                 if constexpr (STORE_NOW) {
 #pragma unroll
                     for (int it = 0; it < 4; ++it)
-                        st16<true>((uint4*)(obase + img * ep.nlog + (size_t)(i32 * 32 + it * 8) * ep.ldc), ov[0][it]);
+                        if (full || row_lane + i32 * 32 + it * 8 < ep.m_valid)
+                            st16<true>((uint4*)(obase + img * ep.nlog + (size_t)(i32 * 32 + it * 8) * ep.ldc), ov[0][it]);
                 }
             }
             };
@@ -743,12 +758,24 @@ gemm_persist_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K,
         // part 2: the next tile's stage 0 (buffer 0) and bias
         issue_next();
         // part 3: this tile's stores (whole 128-B row segments, non-temporal)
+        if (full) {
 #pragma unroll
-        for (int i = 0; i < WTM / 32; ++i)
+            for (int i = 0; i < WTM / 32; ++i)
 #pragma unroll
-            for (int it = 0; it < 4; ++it)
-                st16<true>((uint4*)(obase + (size_t)(i * 32 + it * 8) * ep.ldc), ov[i][it]);
+                for (int it = 0; it < 4; ++it)
+                    st16<true>((uint4*)(obase + (size_t)(i * 32 + it * 8) * ep.ldc), ov[i][it]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < WTM / 32; ++i)
+#pragma unroll
+                for (int it = 0; it < 4; ++it)
+                    if (row_lane + i * 32 + it * 8 < ep.m_valid)
+                        st16<true>((uint4*)(obase + (size_t)(i * 32 + it * 8) * ep.ldc), ov[i][it]);
+        }
         if (!more) break;
+        // the last row panel: fewer than NSTORE stores may follow the next tile's DMA, so the
+        // vmcnt(NSTORE) below would not cover it — drain everything instead
+        if (!full) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         RS_PERSIST_WAIT(16);
         static_assert(NSTORE == 16, "RS_PERSIST_WAIT count");
     }
@@ -1934,6 +1961,56 @@ extern "C" int rs_debug_x3s(int epi, const void* A2, const void* W2, const float
         ep.lnx = lnx; ep.lncnt = (unsigned*)lncnt; ep.lnerr = (unsigned*)lnerr;
     }
     const hipError_t e = launch_gemm_x3s(epi, (const f16*)A2, (const f16*)W2, 2 * K, M_pad, N, K, ep, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : -2;
+}
+
+// Test entry (not part of the scoring path): one launch_gemm(epi, A, W, M_pad, N_pad, K, ep, st, 0)
+// with the caller's EpiArgs fields (mirrored by tests/tail_ref.py GemmEpi), for the epilogues of the
+// last layer and the MLM head transform — EPI_RES_F32, EPI_GELU_F32, EPI_BIAS_F32, EPI_RESLN_F32
+// (res_o16 != null: the deferred form) and EPI_GELU_F16 (kx 1 or 3) — through the production routing
+// (launch_epi).  A [M_pad, K], W [N_pad, K] fp16; out / res [M_pad, ldc] (out a column window of a wider
+// buffer when ldc > N_pad; EPI_GELU_F16: the image [M_pad, ldc >= kx nlog], nlog >= N_pad).
+struct DebugGemmEpi {
+    const float* bias;
+    const float* res;
+    const void* res_stats;
+    const float* res_g;
+    const float* res_b;
+    void* out;
+    const void* res_o16;
+    const void* res_stats0;
+    const float* res_g0;
+    const float* res_b0;
+    int ldc, m_valid, kx, nlog;
+};
+extern "C" int rs_debug_gemm_epi(int epi, const void* A, const void* W, int M_pad, int N_pad, int K,
+                                 const DebugGemmEpi* a, void* stream) {
+    if (!A || !W || !a || !a->bias || !a->out || N_pad <= 0 || K <= 0 || a->m_valid < 0 || a->m_valid > M_pad) return -1;
+    EpiArgs ep{};
+    ep.bias = a->bias; ep.out = a->out; ep.ldc = a->ldc; ep.m_valid = a->m_valid; ep.kx = 1; ep.nlog = N_pad;
+    switch (epi) {
+        case EPI_GELU_F16:
+            if ((a->kx != 1 && a->kx != 3) || a->nlog < N_pad || a->nlog % 8 || a->ldc < a->kx * a->nlog || a->ldc % 8) return -1;
+            ep.kx = a->kx; ep.nlog = a->nlog;
+            break;
+        case EPI_RESLN_F32:
+            if (!a->res_stats || !a->res_g || !a->res_b) return -1;
+            if (a->res_o16 && (!a->res_stats0 || !a->res_g0 || !a->res_b0)) return -1;
+            ep.res_stats = (const float2*)a->res_stats; ep.res_g = a->res_g; ep.res_b = a->res_b;
+            ep.res_o16 = (const f16*)a->res_o16; ep.res_stats0 = (const float2*)a->res_stats0;
+            ep.res_g0 = a->res_g0; ep.res_b0 = a->res_b0;
+            [[fallthrough]];
+        case EPI_RES_F32:
+            if (!a->res) return -1;
+            ep.res = a->res;
+            [[fallthrough]];
+        case EPI_GELU_F32:
+        case EPI_BIAS_F32:
+            if (a->ldc < N_pad || a->ldc % 4) return -1;
+            break;
+        default: return -1;
+    }
+    const hipError_t e = launch_gemm(epi, (const f16*)A, (const f16*)W, M_pad, N_pad, K, ep, (hipStream_t)stream, 0);
     return e == hipSuccess ? 0 : -2;
 }
 

@@ -674,13 +674,12 @@ struct ChunkCtx {
     int head_mlm(float* d_out_rows) {
         if (int r = gemm(RS_K_DECODER, EPI_GELU_F32, false, hq16, m->wt, ns, H, kx * H, bias_ep(m->bt, tq, H), H)) return r;
         LAUNCH_OTHER(launch_ln_rows(tq, ns, m->gt, m->bet, eps, H, hq32, nullptr, hq16, kx, st));
-        LAUNCH_OTHER(launch_gather_labels(d_tok, sm, c.s0, c.s1, m->lab.as<int>(), st));
-        EpiArgs ep{};
-        ep.bias = m->bdec; ep.n_valid = cf.vocab; ep.lse_part = m->part.as<float2>();
-        ep.n_parts = m->vpad / 64; ep.label = m->lab.as<int>(); ep.label_logit = m->llog.as<float>();
-        if (int r = gemm(RS_K_DECODER, EPI_LSE, false, hq16, m->wdec, ns, m->vpad, kx * H, ep, cf.vocab)) return r;
-        LAUNCH_OTHER(launch_lse_finalize(m->part.as<float2>(), m->vpad / 64, m->llog.as<float>(), ns, d_out_rows + c.s0,
-                                         st));
+        const MlmDecoder d{hq16, m->wdec, m->bdec, ns, m->vpad, cf.vocab, kx * H, d_tok, sm, c.s0, m->lab.as<int>(),
+                           m->part.as<float2>(), m->llog.as<float>(), d_out_rows + c.s0};
+        HIPTRY(launch_mlm_decoder(d, st, [&](bool is_gemm, auto&& launch) {
+            ProfScope ps(m, st, is_gemm ? RS_K_DECODER : RS_K_OTHER, is_gemm ? 2.0 * ns * (double)cf.vocab * (kx * H) : 0);
+            return launch();
+        }));
         return RS_OK;
     }
     int head_cls(float* d_out_rows) {

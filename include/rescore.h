@@ -146,7 +146,10 @@ int rs_pll_score(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off, in
  *   d_ids      int32 ragged sequences (already masked), h_seq_off int32 [n_seq+1] host
  *   h_query    int32 [n_seq] host   position of the masked token in each sequence
  *   d_label    int32 [n_seq]        label id at that position
- *   d_out      float32 [n_seq]      log_softmax(logits[query])[label] */
+ *   d_out      float32 [n_seq]      log_softmax(logits[query])[label]
+ * A label outside [0, vocab) here (except -1, which takes the token id at the position), or a
+ * token id outside [0, vocab) at a scored position of rs_pll_score, has log-probability -inf: the
+ * call fails with RS_EUNSUP (the range guard above). */
 int rs_masked_logprob(rs_model* m, const int32_t* d_ids, const int32_t* h_seq_off,
                       const int32_t* h_query, const int32_t* d_label, int32_t n_seq,
                       float* d_out, void* stream);
