@@ -119,6 +119,12 @@ __device__ __forceinline__ void put_split4(f16* row, int c, int K, int kx, float
 __device__ __forceinline__ float2 il_parts(const f16* row, int c) {
     return make_float2((float)row[il_hi(c)], (float)row[il_hi(c) + 32]);
 }
+// the values of columns c .. c + 3 (c % 4 == 0) of a kx == 2 image row
+__device__ __forceinline__ float4 il_load4(const f16* row, int c) {
+    const half4 hi = *(const half4*)(row + il_hi(c)), lo = *(const half4*)(row + il_hi(c) + 32);
+    return make_float4((float)hi[0] + (float)lo[0] * X3_DOWN, (float)hi[1] + (float)lo[1] * X3_DOWN,
+                       (float)hi[2] + (float)lo[2] * X3_DOWN, (float)hi[3] + (float)lo[3] * X3_DOWN);
+}
 
 // Per-sequence metadata of a scoring call (structure of arrays, device).  A "sequence"
 // is one BERT input: a masked copy of a hypothesis (MLM_PLL), a hypothesis
@@ -145,7 +151,7 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
-// ---- launchers (defined in k_gemm.hip / k_bert.hip / k_rerank.hip) ---------------------
+// ---- launchers (defined in k_gemm.hip / k_bert.hip / k_attn.hip / k_rerank.hip) --------
 // tag != 0: the same kernel instantiated under a name-tag option (k_gemm.hip P_TAG_OPROJ /
 // P_TAG_FFN2; the kernel name only, besides RS_GEMM_GROUP_M_FFN2 for tag 2), so
 // rocprofv3 separates the O-projection (tag 1) and BertOutput (tag 2) launches from the QKV
@@ -215,12 +221,12 @@ hipError_t launch_bertscore_recall(const f16* emb, int H, const int* hyp_off, co
 hipError_t launch_embed_out(const float* x32, const float2* stats, const float* g, const float* b,
                             SeqMeta sm, int s0, int s1, int row0, int H, f16* out, hipStream_t st,
                             const f16* himg = nullptr, bool two = false);
-// max_len: longest sequence of the launch (0 = unknown): the 16x16x32 kernel serves chunks whose
-// sequences all fit one 64-key block, the 32x32x16 kernel the others (fewer K/V reloads).
+// H == 64 heads.  max_len > 0: longest sequence of the launch; it and (qkv32, dedup) choose the
+// kernel (table in k_attn.hip): the 16x16x32 kernels serve launches whose sequences all fit one
+// 64-key block, the 32x32x16 kernel the others (fewer K/V reloads).
 // dedup: qkv holds unique rows; sequence s, position t reads row (t == mask_pos ? urow_m : urow_h + t)
 hipError_t launch_attention_full(const void* qkv, bool qkv32, SeqMeta sm, int s0, int s1, int row0,
-                                 int H, int heads, f16* ctx, int kx, hipStream_t st, bool dedup = false,
-                                 int max_len = 0);
+                                 int H, int heads, f16* ctx, int kx, hipStream_t st, bool dedup, int max_len);
 // resq = LN(x32[query row]) (x32 pre-LN, with its row statistics and LN weight / bias)
 hipError_t launch_attention_query(const void* qkv, bool qkv32, const float* x32, const float2* stats,
                                   const float* g, const float* b, SeqMeta sm, int s0, int s1,

@@ -1,8 +1,9 @@
 """GPU: the ragged self-attention kernels vs a torch fp32 reference (eager_attention_forward,
 transformers modeling_bert.py:111-136, scale 64**-0.5, no padding rows), per sequence.
 
-Kernels (k_bert.hip, through the rs_debug_attention diagnostic entry): kind 0 = attn_tr_kernel
-(32x32x16 MFMA), kind 6 = attn16_kernel (16x16x32 MFMA, production default).  Lengths cover
+Kernels (k_attn.hip, through the rs_debug_attention diagnostic entry): kind 0 = attn_tr_kernel
+(32x32x16 MFMA, production's fp16 kernel for a chunk with some T > 64), kind 6 = attn16_kernel
+(16x16x32 MFMA, production's fp16 kernel while every T <= 64).  Lengths cover
 the tile edges of both (1, 15/16/17, 31/32/33, 47/48, 63/64/65) and the online-softmax path
 (T > 64, several key blocks).  Inputs and P are fp16, accumulation fp32: |err| <= 2e-3 on
 O(1) outputs.
