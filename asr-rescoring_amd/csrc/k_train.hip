@@ -4,12 +4,16 @@
 // GEMMs are plain (transposed) fp32 GEMMs on the f32-input MFMA (k_sgemm.hip); everything
 // else is here.  One wave per token row for row-wise ops; column reductions in two stages
 // (64-row partials, then an ordered sum).
+#include <algorithm>
+#include <string>
+#include <vector>
+
 #include "common.h"
 #include "train.h"
 
 namespace {
 
-constexpr float kInvSqrt2 = 0.70710678118654752f;
+constexpr float kInvSqrt2= 0.70710678118654752f;
 constexpr float kInvSqrt2Pi = 0.39894228040143268f;
 
 template <int NV>
@@ -278,6 +282,288 @@ tr_attn_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ P, c
         for (int c = 0; c < 64; c += 4) {
             *(float4*)(o + H + c) = make_float4(dk[c] * 0.125f, dk[c + 1] * 0.125f, dk[c + 2] * 0.125f, dk[c + 3] * 0.125f);
             *(float4*)(o + 2 * H + c) = make_float4(dv[c], dv[c + 1], dv[c + 2], dv[c + 3]);
+        }
+    }
+}
+
+// ---- Tiled attention (any T up to max_pos; fixed LDS footprint) ---------------------------------
+// The same expressions as the pair above on 64 x 64 tiles and the f32-input MFMA
+// (v_mfma_f32_32x32x2_f32: every result an exact k-ordered fp32 fmaf chain).  256 threads, each of
+// the four waves owning one 32 x 32 tile of the block's 64 x 64 output: wave w rows 32 (w & 1),
+// columns 32 (w >> 1).  Operands are natural row-major [64][kTL] LDS images (rows outside the
+// sequence zero-filled), read either with the reduction index contiguous ("KC": a lane's 32
+// values of the 64-deep reduction are 8 ds_read_b128; kTL = 68 floats puts the 16 rows of a
+// lane group on 16 distinct 16-B slots of the 64 banks) or along it ("MC": ds_read_b32 of 32
+// consecutive floats per lane half: conflict-free).  MFMA step kk of lane half h takes reduction
+// index 32 h + kk — the same permutation on both operands, so the product is unchanged.
+// D map: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5).
+typedef float ta_f32x16 __attribute__((ext_vector_type(16)));
+constexpr int kTT = 64, kTL = 68, kTImg = kTT * kTL;
+
+__device__ __forceinline__ void ta_zero(ta_f32x16& a) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) a[r] = 0.f;
+}
+
+// acc[m][n] += sum_k A(m, k) B(n, k) over k = 0..63, m = am0 + (0..31), n = bn0 + (0..31);
+// AKC: A(m, k) = a[m][k], else a[k][m]; BKC alike
+template <bool AKC, bool BKC>
+__device__ __forceinline__ void ta_mma(const float* a, int am0, const float* b, int bn0, int lane, ta_f32x16& acc) {
+    const int c = lane & 31, h = lane >> 5;
+    float fa[32], fb[32];
+    if (AKC) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const float4 v = *(const float4*)(a + (am0 + c) * kTL + 32 * h + 4 * q);
+            fa[4 * q] = v.x; fa[4 * q + 1] = v.y; fa[4 * q + 2] = v.z; fa[4 * q + 3] = v.w;
+        }
+    } else {
+#pragma unroll
+        for (int kk = 0; kk < 32; ++kk) fa[kk] = a[(32 * h + kk) * kTL + am0 + c];
+    }
+    if (BKC) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const float4 v = *(const float4*)(b + (bn0 + c) * kTL + 32 * h + 4 * q);
+            fb[4 * q] = v.x; fb[4 * q + 1] = v.y; fb[4 * q + 2] = v.z; fb[4 * q + 3] = v.w;
+        }
+    } else {
+#pragma unroll
+        for (int kk = 0; kk < 32; ++kk) fb[kk] = b[(32 * h + kk) * kTL + bn0 + c];
+    }
+#pragma unroll
+    for (int kk = 0; kk < 32; ++kk) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[kk], fb[kk], acc, 0, 0, 0);
+}
+
+// img[r][0..63] = src[(row0 + r) * ld + 0..63] for row0 + r < rows, else 0 (64 rows; 16-B accesses)
+__device__ __forceinline__ void ta_load_rows(float* img, const float* src, size_t ld, int row0, int rows, int tid) {
+#pragma unroll
+    for (int q = tid; q < kTT * 16; q += 256) {
+        const int r = q >> 4, c = (q & 15) * 4;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (row0 + r < rows) v = *(const float4*)(src + (size_t)(row0 + r) * ld + c);
+        *(float4*)(img + r * kTL + c) = v;
+    }
+}
+
+// img[r][c] = (drop of) src[(i0 + r) * T + j0 + c] inside the T x T matrix, else 0.  e0: the
+// dropout element index of src[0] (its place in the saved-P layout).
+template <bool DROP>
+__device__ __forceinline__ void ta_load_pp(float* img, const float* src, int T, int i0, int j0, int tid,
+                                           const TrDrop& dr, unsigned long long e0) {
+    const int c = tid & 63;
+#pragma unroll 4
+    for (int r = tid >> 6; r < kTT; r += 4) {
+        float v = 0.f;
+        if (i0 + r < T && j0 + c < T) {
+            const long long o = (long long)(i0 + r) * T + j0 + c;
+            v = src[o];
+            if (DROP) v = tr_drop(dr, e0 + (unsigned long long)o, v);
+        }
+        img[r * kTL + c] = v;
+    }
+}
+
+// Forward of one (64-query tile, head, sequence): scores of the whole row block into P (pass 1,
+// MFMA), a two-pass softmax over the stored row (wave per row), then ctx = drop(P) V (MFMA).
+__global__ void __launch_bounds__(256)
+tr_attn_fwd_tiled_kernel(const float* __restrict__ qkv, const int* __restrict__ seq_off, const int* __restrict__ klen,
+                         const long long* __restrict__ pofs, int H, int heads, float* P, float* __restrict__ ctx,
+                         TrDrop dr) {
+    __shared__ __attribute__((aligned(16))) float sm[3 * kTImg];
+    float *sQ = sm, *sB = sm + kTImg, *sP = sm + 2 * kTImg;
+    const int s = blockIdx.z, hd = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r0 = seq_off[s], T = seq_off[s + 1] - r0, q0 = blockIdx.x * kTT;
+    if (q0 >= T) return;
+    const int TK = klen ? min(max(klen[s], 1), T) : T;
+    const size_t ld = 3 * (size_t)H;
+    const float* base = qkv + (size_t)r0 * ld + hd * 64;
+    const long long pbase = pofs[s] + (long long)hd * T * T;
+    float* Ph = P + pbase;
+    const int wm = 32 * (wave & 1), wn = 32 * (wave >> 1), c = lane & 31, h = lane >> 5;
+    const int nkt = (TK + kTT - 1) / kTT;
+
+    ta_load_rows(sQ, base, ld, q0, T, tid);
+    for (int kt = 0; kt < nkt; ++kt) {
+        const int j0 = kt * kTT;
+        __syncthreads();
+        ta_load_rows(sB, base + H, ld, j0, T, tid);
+        __syncthreads();
+        ta_f32x16 acc;
+        ta_zero(acc);
+        ta_mma<true, true>(sQ, wm, sB, wn, lane, acc);
+        const int j = j0 + wn + c;
+        if (j < TK) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int i = q0 + wm + (r & 3) + 8 * (r >> 2) + 4 * h;
+                if (i < T) Ph[(long long)i * T + j] = acc[r] * 0.125f;
+            }
+        }
+    }
+    __syncthreads();
+    // softmax of rows q0 + wave, + 4, ...: keys j >= TK are padding, probability exactly 0
+    for (int rr = wave; rr < kTT && q0 + rr < T; rr += 4) {
+        float* row = Ph + (long long)(q0 + rr) * T;
+        float m = -INFINITY;
+        for (int j = lane; j < TK; j += 64) m = fmaxf(m, row[j]);
+        m = wave_max(m);
+        float sum = 0.f;
+        for (int j = lane; j < TK; j += 64) {
+            const float e = __expf(row[j] - m);
+            row[j] = e;
+            sum += e;
+        }
+        sum = wave_sum(sum);
+        for (int j = lane; j < T; j += 64) row[j] = j < TK ? row[j] / sum : 0.f;
+    }
+    ta_f32x16 o;
+    ta_zero(o);
+    for (int kt = 0; kt < nkt; ++kt) {
+        const int j0 = kt * kTT;
+        __syncthreads();
+        ta_load_rows(sB, base + 2 * H, ld, j0, T, tid);
+        ta_load_pp<true>(sP, Ph, T, q0, j0, tid, dr, (unsigned long long)pbase);
+        __syncthreads();
+        ta_mma<true, false>(sP, wm, sB, wn, lane, o);
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int i = q0 + wm + (r & 3) + 8 * (r >> 2) + 4 * h;
+        if (i < T) ctx[(size_t)(r0 + i) * H + hd * 64 + wn + c] = o[r];
+    }
+}
+
+// Backward, query side, of one (64-query tile, head, sequence): rd = rowsum(P * drop(dctx V^T))
+// (pass 1), then per key tile dS = P (drop(dctx V^T) - rd), stored to dS (the saved-P layout of
+// one layer) for the key side, and dQ = 0.125 dS K.  dctx V^T is recomputed in pass 2.
+__global__ void __launch_bounds__(256)
+tr_attn_bwd_q_tiled_kernel(const float* __restrict__ qkv, const float* __restrict__ P,
+                           const float* __restrict__ dctx, const int* __restrict__ seq_off,
+                           const long long* __restrict__ pofs, int H, int heads, float* __restrict__ dS,
+                           float* __restrict__ dqkv, TrDrop dr) {
+    __shared__ __attribute__((aligned(16))) float sm[4 * kTImg];
+    __shared__ float s_rd[2][kTT];
+    float *sG = sm, *sV = sm + kTImg, *sK = sm + 2 * kTImg, *sS = sm + 3 * kTImg;
+    const int s = blockIdx.z, hd = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r0 = seq_off[s], T = seq_off[s + 1] - r0, q0 = blockIdx.x * kTT;
+    if (q0 >= T) return;
+    const size_t ld = 3 * (size_t)H;
+    const float* base = qkv + (size_t)r0 * ld + hd * 64;
+    const long long pbase = pofs[s] + (long long)hd * T * T;
+    const float* Ph = P + pbase;
+    float* Sh = dS + pbase;
+    const int wm = 32 * (wave & 1), wn = 32 * (wave >> 1), c = lane & 31, h = lane >> 5;
+    const int nkt = (T + kTT - 1) / kTT;
+
+    ta_load_rows(sG, dctx + (size_t)r0 * H + hd * 64, (size_t)H, q0, T, tid);
+    float rd[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) rd[r] = 0.f;
+    for (int kt = 0; kt < nkt; ++kt) {
+        const int j0 = kt * kTT;
+        __syncthreads();
+        ta_load_rows(sV, base + 2 * H, ld, j0, T, tid);
+        __syncthreads();
+        ta_f32x16 acc;
+        ta_zero(acc);
+        ta_mma<true, true>(sG, wm, sV, wn, lane, acc);
+        const int j = j0 + wn + c;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int i = q0 + wm + (r & 3) + 8 * (r >> 2) + 4 * h;
+            if (i < T && j < T) {
+                const long long o = (long long)i * T + j;
+                rd[r] += Ph[o] * tr_drop(dr, (unsigned long long)(pbase + o), acc[r]);
+            }
+        }
+    }
+    // a row's sum: the 32 lanes of a half (butterfly), then the two column waves in order
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        float v = rd[r];
+#pragma unroll
+        for (int d = 16; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+        if (c == 0) s_rd[wave >> 1][wm + (r & 3) + 8 * (r >> 2) + 4 * h] = v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int il = wm + (r & 3) + 8 * (r >> 2) + 4 * h;
+        rd[r] = s_rd[0][il] + s_rd[1][il];
+    }
+    ta_f32x16 dq;
+    ta_zero(dq);
+    for (int kt = 0; kt < nkt; ++kt) {
+        const int j0 = kt * kTT;
+        __syncthreads();
+        ta_load_rows(sV, base + 2 * H, ld, j0, T, tid);
+        ta_load_rows(sK, base + H, ld, j0, T, tid);
+        __syncthreads();
+        ta_f32x16 acc;
+        ta_zero(acc);
+        ta_mma<true, true>(sG, wm, sV, wn, lane, acc);
+        const int j = j0 + wn + c;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int il = wm + (r & 3) + 8 * (r >> 2) + 4 * h, i = q0 + il;
+            float ds = 0.f;
+            if (i < T && j < T) {
+                const long long o = (long long)i * T + j;
+                ds = Ph[o] * (tr_drop(dr, (unsigned long long)(pbase + o), acc[r]) - rd[r]);
+                Sh[o] = ds;
+            }
+            sS[il * kTL + wn + c] = ds;
+        }
+        __syncthreads();
+        ta_mma<true, false>(sS, wm, sK, wn, lane, dq);
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int i = q0 + wm + (r & 3) + 8 * (r >> 2) + 4 * h;
+        if (i < T) dqkv[(size_t)(r0 + i) * ld + hd * 64 + wn + c] = dq[r] * 0.125f;
+    }
+}
+
+// Backward, key side, of one (64-key tile, head, sequence): dK = 0.125 dS^T Q and
+// dV = drop(P)^T dctx, summed over the query tiles in ascending order in the accumulators
+// (no atomics: bitwise reproducible).  A padding key's column of P and dS is 0: its rows are 0.
+__global__ void __launch_bounds__(256)
+tr_attn_bwd_kv_tiled_kernel(const float* __restrict__ qkv, const float* __restrict__ P,
+                            const float* __restrict__ dS, const float* __restrict__ dctx,
+                            const int* __restrict__ seq_off, const long long* __restrict__ pofs, int H, int heads,
+                            float* __restrict__ dqkv, TrDrop dr) {
+    __shared__ __attribute__((aligned(16))) float sm[4 * kTImg];
+    float *sQ = sm, *sG = sm + kTImg, *sS = sm + 2 * kTImg, *sP = sm + 3 * kTImg;
+    const int s = blockIdx.z, hd = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r0 = seq_off[s], T = seq_off[s + 1] - r0, j0 = blockIdx.x * kTT;
+    if (j0 >= T) return;
+    const size_t ld = 3 * (size_t)H;
+    const float* base = qkv + (size_t)r0 * ld + hd * 64;
+    const long long pbase = pofs[s] + (long long)hd * T * T;
+    const int wm = 32 * (wave & 1), wn = 32 * (wave >> 1), c = lane & 31, h = lane >> 5;
+    const int nqt = (T + kTT - 1) / kTT;
+    ta_f32x16 dk, dv;
+    ta_zero(dk);
+    ta_zero(dv);
+    for (int qt = 0; qt < nqt; ++qt) {
+        const int i0 = qt * kTT;
+        __syncthreads();
+        ta_load_rows(sQ, base, ld, i0, T, tid);
+        ta_load_rows(sG, dctx + (size_t)r0 * H + hd * 64, (size_t)H, i0, T, tid);
+        ta_load_pp<false>(sS, dS + pbase, T, i0, j0, tid, dr, 0);
+        ta_load_pp<true>(sP, P + pbase, T, i0, j0, tid, dr, (unsigned long long)pbase);
+        __syncthreads();
+        ta_mma<false, false>(sS, wm, sQ, wn, lane, dk);
+        ta_mma<false, false>(sP, wm, sG, wn, lane, dv);
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int j = j0 + wm + (r & 3) + 8 * (r >> 2) + 4 * h;
+        if (j < T) {
+            float* o = dqkv + (size_t)(r0 + j) * ld + hd * 64 + wn + c;
+            o[H] = dk[r] * 0.125f;
+            o[2 * H] = dv[r];
         }
     }
 }
@@ -732,6 +1018,91 @@ hipError_t tr_attn_bwd(const float* qkv, const float* P, const float* dctx, cons
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(tr_attn_bwd_kernel, dim3(S, heads), dim3(64), sm, s, qkv, P, dctx, seq_off, pofs, H, heads, dqkv, d);
     return hipGetLastError();
+}
+
+// Tiled forms: any tmax, one launch for the whole (mixed-length) batch; blocks past a sequence's
+// end exit at once.  The backward's dS scratch has the saved-P layout of one layer (pofs[S] floats).
+hipError_t tr_attn_fwd_tiled(const float* qkv, const int* seq_off, const int* klen, const long long* pofs, int S,
+                             int tmax, int H, int heads, float* P, float* ctx, hipStream_t s, const TrDrop& d) {
+    if (S <= 0 || tmax <= 0) return hipSuccess;
+    hipLaunchKernelGGL(tr_attn_fwd_tiled_kernel, dim3((tmax + kTT - 1) / kTT, heads, S), dim3(256), 0, s, qkv, seq_off,
+                       klen, pofs, H, heads, P, ctx, d);
+    return hipGetLastError();
+}
+
+hipError_t tr_attn_bwd_tiled(const float* qkv, const float* P, const float* dctx, const int* seq_off,
+                             const long long* pofs, int S, int tmax, int H, int heads, float* dS, float* dqkv,
+                             hipStream_t s, const TrDrop& d) {
+    if (S <= 0 || tmax <= 0) return hipSuccess;
+    const dim3 grid((tmax + kTT - 1) / kTT, heads, S);
+    hipLaunchKernelGGL(tr_attn_bwd_q_tiled_kernel, grid, dim3(256), 0, s, qkv, P, dctx, seq_off, pofs, H, heads, dS,
+                       dqkv, d);
+    hipLaunchKernelGGL(tr_attn_bwd_kv_tiled_kernel, grid, dim3(256), 0, s, qkv, P, dS, dctx, seq_off, pofs, H, heads,
+                       dqkv, d);
+    return hipGetLastError();
+}
+
+int rs_fail(int code, const std::string& msg);
+
+// Test entry: attention forward then backward on caller-provided fp32 qkv [M, 3H] and dctx [M, H]
+// (device), seq_off [n_seq + 1] and the nullable klen [n_seq] device int32.  form 0: the
+// whole-head kernels (T <= 128); 1: the tiled kernels.  Dropout (seed, step, site, p), p = 0: off.
+extern "C" int rs_debug_train_attn(int form, const float* qkv, const int* seq_off, const int* klen, int n_seq, int H,
+                                   int heads, const float* dctx, unsigned seed, unsigned long long step, unsigned site,
+                                   float p, float* ctx, float* dqkv, void* stream) {
+    if (!qkv || !seq_off || !dctx || !ctx || !dqkv || n_seq <= 0) return rs_fail(RS_EARG, "null argument / empty batch");
+    if (form < 0 || form > 1) return rs_fail(RS_EARG, "form must be 0 or 1");
+    if (heads <= 0 || H != heads * 64) return rs_fail(RS_EUNSUP, "head_dim must be 64");
+    if (!(p >= 0.f && p < 1.f)) return rs_fail(RS_EARG, "p must be in [0, 1)");
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<int> off(n_seq + 1);
+    if (hipMemcpyAsync(off.data(), seq_off, off.size() * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return rs_fail(RS_EHIP, "rs_debug_train_attn: reading seq_off");
+    std::vector<long long> pofs(n_seq + 1, 0);
+    int tmax = 0;
+    for (int s = 0; s < n_seq; ++s) {
+        const long long T = off[s + 1] - off[s];
+        if (off[0] != 0 || T < 1) return rs_fail(RS_EARG, "offsets must start at 0 and ascend");
+        tmax = std::max(tmax, (int)T);
+        pofs[s + 1] = pofs[s] + (long long)heads * T * T;
+    }
+    if (form == 0 && tmax > 128) return rs_fail(RS_EUNSUP, "form 0 is limited to 128 tokens");
+    TrDrop d;
+    d.seed = seed;
+    d.step = (uint32_t)step;
+    d.step_hi = (uint32_t)(step >> 32);
+    d.site = site;
+    d.thresh = p <= 0.f ? 0u : (uint32_t)std::min(4294967295.0, (double)p * 4294967296.0);
+    d.scale = (float)(1.0 / (1.0 - (double)p));
+    // scratch (pofs | P | dS): kept and grown between calls, so a timing loop over this entry
+    // (tools/train_attn_bench.py) measures the kernels and not hipMalloc / hipFree
+    static void* buf = nullptr;
+    static size_t buf_bytes = 0;
+    const size_t np = (size_t)pofs[n_seq], meta = ((size_t)(n_seq + 1) * 8 + 255) & ~(size_t)255;
+    const size_t need = meta + np * 4 * (form == 1 ? 2 : 1);
+    if (need > buf_bytes) {
+        if (buf) (void)hipFree(buf);
+        buf = nullptr;
+        buf_bytes = 0;
+        if (hipMalloc(&buf, need) != hipSuccess) {
+            (void)hipGetLastError();
+            return rs_fail(RS_ENOMEM, "rs_debug_train_attn: scratch");
+        }
+        buf_bytes = need;
+    }
+    long long* d_pofs = (long long*)buf;
+    float* P = (float*)((char*)buf + meta);
+    hipError_t e = hipMemcpyAsync(d_pofs, pofs.data(), pofs.size() * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess)
+        e = form == 1 ? tr_attn_fwd_tiled(qkv, seq_off, klen, d_pofs, n_seq, tmax, H, heads, P, ctx, st, d)
+                      : tr_attn_fwd(qkv, seq_off, klen, d_pofs, n_seq, tmax, H, heads, P, ctx, st, d);
+    if (e == hipSuccess)
+        e = form == 1 ? tr_attn_bwd_tiled(qkv, P, dctx, seq_off, d_pofs, n_seq, tmax, H, heads, P + np, dqkv, st, d)
+                      : tr_attn_bwd(qkv, P, dctx, seq_off, d_pofs, n_seq, tmax, H, heads, dqkv, st, d);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return rs_fail(RS_EHIP, std::string("rs_debug_train_attn: ") + hipGetErrorString(e));
+    return RS_OK;
 }
 
 hipError_t tr_ln_bwd(const float* dy, const float* x, const float2* st, const float* g, float* dx, int M, int H,

@@ -72,11 +72,20 @@ hipError_t tr_bias_gelu(float* pre, const float* bias, float* act, int M, int N,
 hipError_t tr_gelu_bwd(float* d, const float* pre, long long n, hipStream_t s);
 hipError_t tr_bias(float* y, const float* bias, int M, int N, hipStream_t s);
 // klen (nullable): sequence s attends to its first klen[s] tokens only (padded-batch rows)
-// P saved before dropout; ctx = drop(P) V
+// P saved before dropout; ctx = drop(P) V.  The whole-head forms: a head's K, V (and the backward's
+// [T][T] dS) in LDS, tmax <= 128.
 hipError_t tr_attn_fwd(const float* qkv, const int* seq_off, const int* klen, const long long* pofs, int S,
                        int tmax, int H, int heads, float* P, float* ctx, hipStream_t s, const TrDrop& d = TrDrop());
 hipError_t tr_attn_bwd(const float* qkv, const float* P, const float* dctx, const int* seq_off, const long long* pofs,
                        int S, int tmax, int H, int heads, float* dqkv, hipStream_t s, const TrDrop& d = TrDrop());
+// The tiled forms (64 x 64 tiles on the f32-input MFMA, fixed LDS footprint): any T, the same
+// expressions and the same saved-P / dropout-index layout.  dS: backward scratch of pofs[S] floats.
+hipError_t tr_attn_fwd_tiled(const float* qkv, const int* seq_off, const int* klen, const long long* pofs, int S,
+                             int tmax, int H, int heads, float* P, float* ctx, hipStream_t s,
+                             const TrDrop& d = TrDrop());
+hipError_t tr_attn_bwd_tiled(const float* qkv, const float* P, const float* dctx, const int* seq_off,
+                             const long long* pofs, int S, int tmax, int H, int heads, float* dS, float* dqkv,
+                             hipStream_t s, const TrDrop& d = TrDrop());
 hipError_t tr_ln_bwd(const float* dy, const float* x, const float2* st, const float* g, float* dx, int M, int H,
                      hipStream_t s);
 size_t tr_colsum_scratch(int M, int N);

@@ -35,6 +35,17 @@ namespace {
         hipError_t e_ = (expr);                                                             \
         if (e_ != hipSuccess) return rs_fail(RS_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
+// allocations: out of memory comes back as RS_ENOMEM (the saved attention probabilities of long
+// batches are the large one: layers * sum_s heads * T_s^2 * 4 bytes)
+#define TRY_ALLOC(expr)                                                                     \
+    do {                                                                                    \
+        hipError_t e_ = (expr);                                                             \
+        if (e_ == hipErrorOutOfMemory) {                                                    \
+            (void)hipGetLastError();                                                        \
+            return rs_fail(RS_ENOMEM, std::string(#expr) + ": out of device memory");       \
+        }                                                                                   \
+        if (e_ != hipSuccess) return rs_fail(RS_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
 #define TRY_BLAS(expr)                                                                      \
     do {                                                                                    \
         rocblas_status s_ = (expr);                                                         \
@@ -74,6 +85,7 @@ struct rs_trainer {
     bool finalized = false;
     rocblas_handle blas = nullptr;
     bool use_rocblas = false;                                 // RS_TRAIN_ROCBLAS=1 (baseline)
+    int attn_mode = 0;              // RS_TRAIN_ATTN: 0 auto (tiled above 128 tokens), 1 tiled, 2 legacy
     std::map<std::string, std::pair<size_t, size_t>> table;   // HF key -> (offset, numel) in floats
     std::vector<float> host;                                  // staged parameters until finalize
     std::vector<char> set;                                    // per table entry: provided?
@@ -180,8 +192,16 @@ int rs_trainer_create(const rs_bert_cfg* cfg, int device, rs_trainer** out) {
     if (c.heads_mask == RS_HEAD_MLM && c.vocab % 4) return rs_fail(RS_EUNSUP, "MLM training needs vocab % 4 == 0");
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return rs_fail(RS_EHIP, "no such HIP device");
+    int attn_mode = 0;
+    if (const char* v = getenv("RS_TRAIN_ATTN")) {
+        const std::string m(v);
+        if (m == "tiled") attn_mode = 1;
+        else if (m == "legacy") attn_mode = 2;
+        else if (!m.empty() && m != "auto") return rs_fail(RS_EARG, "RS_TRAIN_ATTN must be auto, tiled or legacy");
+    }
     rs_trainer* t = new (std::nothrow) rs_trainer();
     if (!t) return rs_fail(RS_ENOMEM, "alloc");
+    t->attn_mode = attn_mode;
     t->cfg = c;
     t->device = device;
     const size_t H = c.hidden, F = c.intermediate, V = c.vocab;
@@ -316,6 +336,8 @@ struct StepCtx {
     struct LA { float *hin, *qkv, *P, *ctx, *x1, *h1, *pre, *act, *x2; float2 *st1, *st2; };
     std::vector<LA> la;
     float *dA = nullptr, *dB = nullptr, *dQKV = nullptr, *dF = nullptr, *part = nullptr, *tail = nullptr;
+    bool tiled = false;             // attention form of this step (whole batch, one launch)
+    float* dS = nullptr;            // tiled backward: dS of one layer, the saved-P layout
     // MLM head (RS_HEAD_MLM): transform pre-GELU / GELU out (pre-LN) / LN out, stats, logits
     float *tpre = nullptr, *tx = nullptr, *th = nullptr, *logits = nullptr;
     float2* tst = nullptr;
@@ -367,7 +389,11 @@ int prepare(StepCtx& c, const int32_t* d_tok, const int32_t* h_off, int n_seq, c
         c.tmax = std::max(c.tmax, T);
     }
     if (c.tmax > cf.max_pos) return rs_fail(RS_EUNSUP, "sequence longer than max_position_embeddings");
-    if (c.tmax > 128) return rs_fail(RS_EUNSUP, "training sequences are limited to 128 tokens");
+    // attention form: the whole-head kernels hold K, V and dS of a head in LDS (T <= 128); a batch
+    // with a longer sequence runs the tiled kernels for every sequence in it
+    c.tiled = t->attn_mode == 1 || (t->attn_mode == 0 && c.tmax > 128);
+    if (!c.tiled && c.tmax > 128)
+        return rs_fail(RS_EUNSUP, "training sequences are limited to 128 tokens (RS_TRAIN_ATTN=legacy)");
     if (h_klen)
         for (int s = 0; s < n_seq; ++s)
             if (h_klen[s] < 1 || h_klen[s] > h_off[s + 1] - h_off[s])
@@ -423,7 +449,7 @@ int prepare(StepCtx& c, const int32_t* d_tok, const int32_t* h_off, int n_seq, c
         c.i_klen = hm.size();
         hm.insert(hm.end(), h_klen, h_klen + S);
     }
-    TRY_HIP(t->meta.ensure(hm.size() * 4));
+    TRY_ALLOC(t->meta.ensure(hm.size() * 4));
     TRY_HIP(hipMemcpyAsync(t->meta.p, hm.data(), hm.size() * 4, hipMemcpyHostToDevice, st));
     c.dm = (const int*)t->meta.p;
     c.pofs = (const long long*)c.dm;
@@ -439,12 +465,13 @@ int prepare(StepCtx& c, const int32_t* d_tok, const int32_t* h_off, int n_seq, c
     const size_t per_layer = MH + QKV + PS + MH + MH + M2 + MH + 2 * MF + MH + M2;
     const size_t n_head = mlm ? 3 * MH + M2 + MV : 0;
     const size_t n_act = MH + M2 + NL * per_layer + MH + n_head;
-    TRY_HIP(t->act.ensure(n_act * 4));
+    TRY_ALLOC(t->act.ensure(n_act * 4));
     const int widest = std::max(std::max(3 * H, F), mlm ? cf.vocab : 0);
     const size_t n_part = al(tr_colsum_scratch(M, widest) / 4);
-    const size_t n_grad = 2 * MH + QKV + MF + n_part + 2 * (size_t)S + aux.size() + M + 64;
-    TRY_HIP(t->grad.ensure(n_grad * 4));
-    TRY_HIP(t->ws.ensure(std::max<size_t>(sgemm_ws_floats(cf, M), 64) * 4));
+    const size_t n_tail = al(2 * (size_t)S + aux.size() + M + 64);
+    const size_t n_grad = 2 * MH + QKV + MF + n_part + n_tail + (c.tiled ? PS : 0);
+    TRY_ALLOC(t->grad.ensure(n_grad * 4));
+    TRY_ALLOC(t->ws.ensure(std::max<size_t>(sgemm_ws_floats(cf, M), 64) * 4));
     float* A = t->act.f();
     c.x0 = A;
     c.st0 = (float2*)(c.x0 + MH);
@@ -480,6 +507,7 @@ int prepare(StepCtx& c, const int32_t* d_tok, const int32_t* h_off, int n_seq, c
     c.dF = c.dQKV + QKV;
     c.part = c.dF + MF;
     c.tail = c.part + n_part;        // per-sequence / per-row small arrays
+    c.dS = c.tiled ? c.tail + n_tail : nullptr;
     return RS_OK;
 }
 
@@ -496,8 +524,13 @@ int encoder_forward(StepCtx& c) {
         StepCtx::LA& a = c.la[l];
         RS_TRY(gemm_nt(t, st, M, 3 * H, H, a.hin, Pm + L.wqkv, a.qkv, 0.f));
         TRY_HIP(tr_bias(a.qkv, Pm + L.bqkv, M, 3 * H, st));
-        TRY_HIP(tr_attn_fwd(a.qkv, c.seq, c.i_klen ? c.dm + c.i_klen : nullptr, c.pofs, c.S, c.tmax, H, nh, a.P,
-                            a.ctx, st, c.drop(1 + 3 * l, true)));
+        const int* klen = c.i_klen ? c.dm + c.i_klen : nullptr;
+        if (c.tiled)
+            TRY_HIP(tr_attn_fwd_tiled(a.qkv, c.seq, klen, c.pofs, c.S, c.tmax, H, nh, a.P, a.ctx, st,
+                                      c.drop(1 + 3 * l, true)));
+        else
+            TRY_HIP(tr_attn_fwd(a.qkv, c.seq, klen, c.pofs, c.S, c.tmax, H, nh, a.P, a.ctx, st,
+                                c.drop(1 + 3 * l, true)));
         RS_TRY(gemm_nt(t, st, M, H, H, a.ctx, Pm + L.wo, a.x1, 0.f));
         TRY_HIP(tr_bias_res_ln(a.x1, Pm + L.bo, a.hin, M, Pm + L.g1, Pm + L.be1, cf.ln_eps, H, a.st1, a.h1, st,
                                c.drop(2 + 3 * l, false)));
@@ -551,7 +584,11 @@ int encoder_backward(StepCtx& c) {
         TRY_HIP(tr_colsum(dBs, nullptr, nullptr, M, H, 0, part, Gm + L.bo, 0, st));
         RS_TRY(gemm_tn(t, st, M, H, H, dBs, a.ctx, Gm + L.wo, 0.f));
         RS_TRY(gemm_nn(t, st, M, H, H, dBs, Pm + L.wo, dA, 0.f));                    // dA = d ctx
-        TRY_HIP(tr_attn_bwd(a.qkv, a.P, dA, c.seq, c.pofs, c.S, c.tmax, H, nh, dQKV, st, c.drop(1 + 3 * l, true)));
+        if (c.tiled)
+            TRY_HIP(tr_attn_bwd_tiled(a.qkv, a.P, dA, c.seq, c.pofs, c.S, c.tmax, H, nh, c.dS, dQKV, st,
+                                      c.drop(1 + 3 * l, true)));
+        else
+            TRY_HIP(tr_attn_bwd(a.qkv, a.P, dA, c.seq, c.pofs, c.S, c.tmax, H, nh, dQKV, st, c.drop(1 + 3 * l, true)));
         TRY_HIP(tr_colsum(dQKV, nullptr, nullptr, M, 3 * H, 0, part, Gm + L.bqkv, 0, st));
         RS_TRY(gemm_tn(t, st, M, 3 * H, H, dQKV, a.hin, Gm + L.wqkv, 0.f));
         TRY_HIP(hipMemcpyAsync(dA, dB, MH * 4, hipMemcpyDeviceToDevice, st));      // residual

@@ -272,7 +272,14 @@ typedef struct rs_train_opts {
 } rs_train_opts;
 
 /* cfg->heads_mask: RS_HEAD_CLS (RescoreBert) or RS_HEAD_MLM (MLM fine-tuning); shapes as
- * rs_model_create (T <= 128 per sequence). */
+ * rs_model_create (T <= max_pos per sequence).  A step keeps the attention probabilities of every
+ * layer for its backward: layers * sum_s heads * T_s^2 * 4 bytes over the batch's sequences (32
+ * rows of 512 tokens on the BERT-base shape: 4.8 GB), plus one layer's worth of scratch when the
+ * batch has a sequence of more than 128 tokens; a step whose buffers do not fit fails with
+ * RS_ENOMEM.  RS_TRAIN_ATTN (read here): auto (default: the whole-head attention kernels while
+ * every sequence of a batch has at most 128 tokens, the tiled kernels for a batch with a longer
+ * one), tiled (the tiled kernels at every length) or legacy (the whole-head kernels only: longer
+ * sequences fail with RS_EUNSUP); any other value fails with RS_EARG. */
 int rs_trainer_create(const rs_bert_cfg* cfg, int device, rs_trainer** out);
 int rs_trainer_set_tensor(rs_trainer* t, const char* hf_key, const void* host_ptr, int dtype,
                           const int64_t* shape, int ndim);
