@@ -60,6 +60,8 @@ _SIGS = {
     "rs_model_reserve": (ctypes.c_int, [P, I64]),
     "rs_pll_score": (ctypes.c_int, [P, P, P, I32, P, P, P]),
     "rs_masked_logprob": (ctypes.c_int, [P, P, P, P, P, I32, P, P]),
+    "rs_masked_topk": (ctypes.c_int, [P, P, P, P, I32, I32, P, P, P]),
+    "rs_pll_topk": (ctypes.c_int, [P, P, P, I32, I32, P, P, P, P, P]),
     "rs_cls_score": (ctypes.c_int, [P, P, P, I32, P, P]),
     "rs_profile_enable": (ctypes.c_int, [P, ctypes.c_int]),
     "rs_profile_read": (ctypes.c_int, [P, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
@@ -120,6 +122,8 @@ _DEBUG_SIGS = {
     "rs_debug_gemm_epi": (CI, [CI, P, P, CI, CI, CI, P, P]),
     # (A, W, bias, label, M_pad, m_valid, vpad, vocab, K, lab, part, llog, out, stream)
     "rs_debug_decoder": (CI, [P, P, P, P, CI, CI, CI, CI, CI, P, P, P, P, P]),
+    # rs_debug_decoder's arguments up to out, then (k, cand, top_id, top_lp, stream)
+    "rs_debug_decoder_topk": (CI, [P, P, P, P, CI, CI, CI, CI, CI, P, P, P, P, CI, P, P, P, P]),
     # (qkv, qkv32, len, row, query, s0, s1, row0, H, heads, kx, qd, x32, stats, g, b, himg, ctxq, resq, stream)
     "rs_debug_attention_query": (CI, [P, CI, P, P, P, CI, CI, CI, CI, CI, CI, P, P, P, P, P, P, P, P, P]),
     # (form, qkv, seq_off, klen, n_seq, H, heads, dctx, seed, step, site, p, ctx, dqkv, stream)

@@ -1,6 +1,7 @@
 """Command-line drivers with the reference's entry points, YAML keys and output files.
 
   python -m asr_rescoring_amd.cli mlm_pll     --config score.yaml    # MLM_PLL/main.py (task: scoring)
+  python -m asr_rescoring_amd.cli mlm_topk    --config score.yaml    # top-k tokens per position ({split}_topk.json)
   python -m asr_rescoring_amd.cli mlm_finetune --config train.yaml   # MLM_PLL/main.py (task: train)
   python -m asr_rescoring_amd.cli rescorebert --config MD_score.yaml # RescoreBert/main.py (task: scoring)
   python -m asr_rescoring_amd.cli rescorebert_train --config MD.yaml # RescoreBert/main.py (task: train)
@@ -116,6 +117,40 @@ def mlm_pll(cfg) -> Dict[str, str]:
     if world > 1:
         import torch.distributed as dist
         dist.barrier()
+    return out_files
+
+
+def mlm_topk(cfg) -> Dict[str, str]:
+    """The model's ``top_k`` (default 5) preferred tokens at every position of the first ``n_best``
+    (default 1) hypotheses of ``max_utt`` utterances — ``logits[range(B), mask_pos]`` of
+    MLM_PLL/main.py:101-105 before the label gather, through ``PLLScorer.topk_nbest``.  No reference
+    counterpart.  For each split with ``{split}_hyps_text_path`` writes ``{split}_topk.json``:
+    ``{utt: {hyp: {"ids": [[k ids] per position], "logprob": [[k floats] per position]}}}``.
+    Weight, tokenizer, precision, device and ``max_rows`` keys as ``mlm_pll``; single-process."""
+    from .scorer import PLLScorer
+    scorer = PLLScorer(_weights(cfg, "mlm"), BERT_BASE, device=_dev(cfg), max_rows=get(cfg, "max_rows", 65536),
+                       precision=get(cfg, "precision", "fp16x3"))
+    k = int(get(cfg, "top_k", 5))
+    out_files = {}
+    for split in ("train", "dev", "test"):
+        text_path = get(cfg, f"{split}_hyps_text_path")
+        if not (text_path and os.path.exists(text_path)):
+            continue
+        hyps = _load(text_path)
+        tok = _tokenizer(cfg, [t for h in hyps.values() for t in h.values()])
+        nb, keys = _nbest_tokens(hyps, tok, int(get(cfg, "max_utt", 1 << 30)), int(get(cfg, "n_best", 1)))
+        ids, lp = scorer.topk_nbest(nb.tokens, nb.hyp_off, k)
+        ids, lp = ids.cpu().tolist(), lp.cpu().tolist()
+        row_off = np.concatenate([[0], np.cumsum(np.diff(nb.hyp_off) - 2)])
+        out = {}
+        for h, (u, hid) in enumerate(keys):
+            a, b = int(row_off[h]), int(row_off[h + 1])
+            out.setdefault(u, {})[hid] = {"ids": ids[a:b], "logprob": lp[a:b]}
+        path = cfg.output_path + f"{split}_topk.json"
+        with open(path, "w", encoding="utf-8") as f:
+            json.dump(out, f, ensure_ascii=False)
+        out_files[split] = path
+    scorer.close()
     return out_files
 
 
@@ -465,7 +500,7 @@ def _logger(path):
     return log
 
 
-COMMANDS = {"mlm_pll": mlm_pll, "mlm_finetune": mlm_finetune, "rescorebert": rescorebert,
+COMMANDS = {"mlm_pll": mlm_pll, "mlm_topk": mlm_topk, "mlm_finetune": mlm_finetune, "rescorebert": rescorebert,
             "rescorebert_train": rescorebert_train,
             "rescore": rescore, "rmbr": rmbr}
 

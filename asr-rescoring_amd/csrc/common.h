@@ -24,6 +24,7 @@ enum EpiKind {
     EPI_LNRES_IMG = 7,  // h <- image(LN(acc + bias + h)), h the two-part image in out, in place
                         //   (split-operand residual blocks; row statistics exchanged between the
                         //   column tiles of a row panel inside the launch: gemm_x3s_kernel)
+    EPI_LSE_TOPK = 8,   // EPI_LSE, and per (row, 64-column slab) its best topk_k (logit, column) pairs
 };
 
 struct EpiArgs {
@@ -63,7 +64,13 @@ struct EpiArgs {
     float ln_eps;
     int diag;              // EPI_LNRES_IMG: 8 = every wait times out (RS_LNFUSE_DIAG, tests); 0 in production
     unsigned long long* dbg;  // stamp builds only (rs_debug_stamps): per-workgroup phase cycle sums
+    // EPI_LSE_TOPK: topk_cand [M, n_parts, topk_k] (logit, column bits), best first (larger logit,
+    // then lower column); slots past a slab's valid columns hold (-inf, INT_MAX)
+    float2* topk_cand;
+    int topk_k;            // 1 .. TOPK_MAX
 };
+constexpr int TOPK_MAX = 16;         // == RS_TOPK_MAX (rescore.h)
+constexpr int TOPK_SUB_ROWS = 2048;  // rows per decoder launch of the top-k form (bounds topk_cand)
 // <= 4 column tiles of 256 rows x 2 statistics granules, then one list-claim granule per row panel
 inline size_t lnres_granules(int m_pad) { return (size_t)m_pad * 4 * 2 + (size_t)m_pad / 256 + 1; }
 
@@ -275,6 +282,45 @@ hipError_t launch_mlm_decoder(const MlmDecoder& d, hipStream_t st, Wrap&& wrap) 
     if (hipError_t e = wrap(true, [&] { return launch_gemm(EPI_LSE, d.A, d.W, m_pad, d.vpad, d.K, ep, st, 0); }))
         return e;
     return wrap(false, [&] { return launch_lse_finalize(d.part, d.vpad / 64, d.llog, d.m_valid, d.out, st); });
+}
+// The same decoder with the model's k preferred tokens of every row: top_id / top_lp [m_valid, k],
+// ordered by (larger logit, lower column), top_lp[i][j] = logit - logsumexp of row i, formed from the
+// same slab (max, sum exp) pairs as out (a returned label's log-prob is out's, bitwise).  The GEMM
+// runs as EPI_LSE_TOPK over sub-batches of TOPK_SUB_ROWS rows, so that the candidate workspace cand
+// stays at topk_cand_bytes(vpad) whatever m_valid is; each sub-batch is merged (topk_merge) before
+// the next overwrites cand.  part / llog / out are those of launch_mlm_decoder, bit for bit: a
+// row's slab pairs do not depend on the rows launched with it.
+struct MlmTopk {
+    int k;                 // 1 .. min(TOPK_MAX, vocab)
+    float2* cand;          // topk_cand_bytes(vpad)
+    int* top_id;           // [m_valid, k]
+    float* top_lp;         // [m_valid, k]
+};
+inline size_t topk_cand_bytes(int vpad) { return (size_t)TOPK_SUB_ROWS * (size_t)(vpad / 64) * TOPK_MAX * sizeof(float2); }
+hipError_t launch_topk_merge(const float2* part, int n_parts, const float2* cand, int k, int rows, int* top_id,
+                             float* top_lp, hipStream_t st);
+template <class Wrap>
+hipError_t launch_mlm_decoder_topk(const MlmDecoder& d, const MlmTopk& t, hipStream_t st, Wrap&& wrap) {
+    if (t.k < 1 || t.k > TOPK_MAX || t.k > d.vocab) return hipErrorInvalidValue;
+    if (hipError_t e = wrap(false, [&] { return launch_gather_labels(d.tok, d.sm, d.s0, d.s0 + d.m_valid, d.lab, d.llog, st); }))
+        return e;
+    const int n_parts = d.vpad / 64, al = gemm_row_align();
+    for (int r0 = 0; r0 < d.m_valid; r0 += TOPK_SUB_ROWS) {
+        const int n = d.m_valid - r0 < TOPK_SUB_ROWS ? d.m_valid - r0 : TOPK_SUB_ROWS;
+        EpiArgs ep{};
+        ep.bias = d.bias; ep.m_valid = n; ep.n_valid = d.vocab; ep.lse_part = d.part + (size_t)r0 * n_parts;
+        ep.n_parts = n_parts; ep.label = d.lab + r0; ep.label_logit = d.llog + r0;
+        ep.topk_cand = t.cand; ep.topk_k = t.k;
+        const f16* A = d.A + (size_t)r0 * d.K;
+        if (hipError_t e = wrap(true, [&] { return launch_gemm(EPI_LSE_TOPK, A, d.W, (n + al - 1) / al * al, d.vpad, d.K, ep, st, 0); }))
+            return e;
+        if (hipError_t e = wrap(false, [&] {
+                return launch_topk_merge(ep.lse_part, n_parts, t.cand, t.k, n, t.top_id + (size_t)r0 * t.k,
+                                         t.top_lp + (size_t)r0 * t.k, st);
+            }))
+            return e;
+    }
+    return wrap(false, [&] { return launch_lse_finalize(d.part, n_parts, d.llog, d.m_valid, d.out, st); });
 }
 hipError_t launch_cls_linear(const float* h, int rows, int H, const float* w, const float* b,
                              float* out, hipStream_t st);

@@ -5,6 +5,8 @@
 //  ln_rows         LayerNorm of BertSelfOutput / BertOutput / head transform (eps 1e-12)
 //  lse_finalize    merges the decoder epilogue's (max, sum exp) slabs: log_softmax gather
 //                  (MLM_PLL/main.py:101-105)
+//  topk_merge      merges the decoder epilogue's per-slab (logit, column) candidates into a row's
+//                  k best tokens and their log-probs (the same row before the label gather)
 //  cls_linear      RescoreBert Linear(H, 1) on the CLS state (RescoreBert/model.py:19-20)
 //  segsum_f64      per-hypothesis PLL, float64, in row order (MLM_PLL/main.py:106-107)
 //
@@ -320,6 +322,67 @@ lse_finalize_kernel(const float2* __restrict__ part, int n_parts, const float* _
     if (lane == 0) out[row] = ll[row] - (mx + logf(sm));
 }
 
+// Merges a row's n_parts x k slab candidates (EPI_LSE_TOPK: (logit, column bits), unused slots
+// (-inf, INT_MAX)) into its k best, in the epilogue's total order — larger logit first, the lower
+// column among equal logits — so the result does not depend on the slab a column fell in.  One wave
+// per row.  The columns are distinct, so the order is strict and round t takes the best candidate
+// that comes after round t-1's winner: nothing is marked, the candidates are only read.  An unused
+// slot is never better than the start value (-inf, INT_MAX), so it is never returned; a row with
+// fewer than k finite logits gets id -1 / log-prob -inf there (the call's range guard reports it).
+// mx and sm are lse_finalize_kernel's loops, statement for statement: top_lp of a label equals that
+// kernel's output for it bit for bit.
+__global__ void __launch_bounds__(256)
+topk_merge_kernel(const float2* __restrict__ part, int n_parts, const float2* __restrict__ cand, int k, int rows,
+                  int* __restrict__ top_id, float* __restrict__ top_lp) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    const float2* p = part + (size_t)row * n_parts;
+    float mx = -INFINITY;
+    for (int q = lane; q < n_parts; q += 64)
+        if (p[q].y > 0.f) mx = fmaxf(mx, p[q].x);
+    mx = wave_max(mx);
+    float sm = 0.f;
+    for (int q = lane; q < n_parts; q += 64)
+        if (p[q].y > 0.f) sm += p[q].y * __expf(p[q].x - mx);
+    sm = wave_sum(sm);
+    const float lse = mx + logf(sm);
+    const float2* c = cand + (size_t)row * n_parts * k;
+    const int n = n_parts * k;
+    float pv = INFINITY;                       // the previous round's winner
+    int pc = -1;
+    for (int t = 0; t < k; ++t) {
+        float bv = -INFINITY;
+        int bc = 0x7fffffff;
+        for (int i = lane; i < n; i += 64) {
+            const float2 e = c[i];
+            const float x = e.x;
+            const int col = __float_as_int(e.y);
+            const bool after = x < pv || (x == pv && col > pc);
+            const bool better = x > bv || (x == bv && col < bc);
+            if (after && better) {
+                bv = x;
+                bc = col;
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(bv, o);
+            const int oc = __shfl_xor(bc, o);
+            if (ov > bv || (ov == bv && oc < bc)) {
+                bv = ov;
+                bc = oc;
+            }
+        }
+        if (lane == 0) {
+            top_id[(size_t)row * k + t] = bv == -INFINITY ? -1 : bc;
+            top_lp[(size_t)row * k + t] = bv - lse;
+        }
+        pv = bv;
+        pc = bc;
+    }
+}
+
 __global__ void __launch_bounds__(256)
 cls_linear_kernel(const float* __restrict__ h, int rows, int H, const float* __restrict__ w,
                   const float* __restrict__ b, float* __restrict__ out) {
@@ -485,6 +548,15 @@ hipError_t launch_lse_finalize(const float2* part, int n_parts, const float* lab
     return hipGetLastError();
 }
 
+hipError_t launch_topk_merge(const float2* part, int n_parts, const float2* cand, int k, int rows, int* top_id,
+                             float* top_lp, hipStream_t st) {
+    if (rows <= 0) return hipSuccess;
+    if (k < 1 || k > TOPK_MAX) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(topk_merge_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, part, n_parts, cand, k, rows, top_id,
+                       top_lp);
+    return hipGetLastError();
+}
+
 hipError_t launch_cls_linear(const float* h, int rows, int H, const float* w, const float* b,
                              float* out, hipStream_t st) {
     if (rows <= 0) return hipSuccess;
@@ -515,6 +587,26 @@ extern "C" int rs_debug_decoder(const void* A, const void* W, const float* bias,
     const MlmDecoder d{(const f16*)A, (const f16*)W, bias, m_valid, vpad, vocab, K, nullptr, sm, 0, lab,
                        (float2*)part, llog, out};
     const hipError_t e = launch_mlm_decoder(d, (hipStream_t)stream, [](bool, auto&& launch) { return launch(); });
+    return e == hipSuccess ? 0 : -2;
+}
+
+// Test entry (not part of the scoring path): the top-k form of the decoder as head_mlm runs it
+// (launch_mlm_decoder_topk).  Arguments as rs_debug_decoder, then k (1 .. 16, <= vocab), the
+// caller's cand [min(M_pad, 2048), vpad / 64, k] (float2) and the outputs top_id (int) / top_lp
+// [m_valid, k].
+extern "C" int rs_debug_decoder_topk(const void* A, const void* W, const float* bias, const int* label, int M_pad,
+                                     int m_valid, int vpad, int vocab, int K, int* lab, void* part, float* llog, float* out,
+                                     int k, void* cand, int* top_id, float* top_lp, void* stream) {
+    if (!A || !W || !bias || !label || !lab || !part || !llog || !out || !cand || !top_id || !top_lp) return -1;
+    if (m_valid <= 0 || M_pad != (m_valid + 255) / 256 * 256 || vpad <= 0 || vpad % 128 || vocab <= 0 || vocab > vpad ||
+        K <= 0 || K % 64 || k < 1 || k > TOPK_MAX || k > vocab)
+        return -1;
+    SeqMeta sm{};
+    sm.label = label;
+    const MlmDecoder d{(const f16*)A, (const f16*)W, bias, m_valid, vpad, vocab, K, nullptr, sm, 0, lab,
+                       (float2*)part, llog, out};
+    const MlmTopk t{k, (float2*)cand, top_id, top_lp};
+    const hipError_t e = launch_mlm_decoder_topk(d, t, (hipStream_t)stream, [](bool, auto&& launch) { return launch(); });
     return e == hipSuccess ? 0 : -2;
 }
 

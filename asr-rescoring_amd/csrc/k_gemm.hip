@@ -95,13 +95,14 @@ gemm_f16_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
     constexpr int WTM = BM / WM, WTN = BN / WN;
     // MFMA shape: 16x16x32 everywhere except the logsumexp epilogue, whose in-register row
     // reductions are written for the 32x32x16 accumulator layout
-    constexpr int MS = EPI == EPI_LSE ? 32 : 16;
+    constexpr bool LSE = EPI == EPI_LSE || EPI == EPI_LSE_TOPK;   // the decoder forms
+    constexpr int MS = LSE ? 32 : 16;
     // non-temporal epilogue stores (st16) for the fp16 outputs only
     constexpr bool NT = EPI == EPI_BIAS_F16 || EPI == EPI_GELU_F16;
     constexpr int KPS = 512 / MS, CPS = KPS / 8, NQ = MS * MS / 256;
     typedef typename AccT<MS>::type accT;
     constexpr int TM = WTM / MS, TN = WTN / MS;
-    static_assert(MS == 32 || (EPI != EPI_LSE && BK / KPS >= 2), "16x16x32 MFMA: not the logsumexp epilogue");
+    static_assert(MS == 32 || (!LSE && BK / KPS >= 2), "16x16x32 MFMA: not the logsumexp epilogue");
     constexpr int RB = BK * 2;            // LDS row bytes
     constexpr int CPR = BK / 8;           // 16-byte chunks per row
     constexpr int RPP = 1024 / RB;        // rows per 1 KiB LDS-DMA piece
@@ -183,7 +184,7 @@ gemm_f16_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
                 // decoder bias can be far larger than the products (a logit offset of 200): started at
                 // the bias, every one of the K / 16 MFMA steps rounds at its magnitude, and the
                 // log-prob loses |b| sqrt(K) 2^-24 (tests/test_gpu_gemm_epi.py, slab_spread)
-                const float4 b4 = EPI == EPI_LSE ? make_float4(0.f, 0.f, 0.f, 0.f) : *(const float4*)(ep.bias + col);
+                const float4 b4 = LSE ? make_float4(0.f, 0.f, 0.f, 0.f) : *(const float4*)(ep.bias + col);
                 float4 lg4, lb4, lg04, lb04;
                 if constexpr (EPI == EPI_RESLN_F32) {
                     lg4 = *(const float4*)(ep.res_g + col);
@@ -300,7 +301,7 @@ gemm_f16_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
     //   row = m0 + wm*WTM + 32i + (lane&31),  col = n0 + wn*WTN + 32j + 8g + 4(lane>>5)
     const int rbase = m0 + wm * WTM + frow;
     const int cbase = n0 + wn * WTN + 4 * fh;
-    if constexpr (EPI == EPI_LSE) {
+    if constexpr (LSE) {
         static_assert(WTN == 64, "decoder logsumexp parts are 64-column slabs (n_parts = N/64)");
         // per (row, 64-column wave slab): max and sum exp over the slab + label logit
         const int slab = (n0 + wn * WTN) / WTN;
@@ -338,6 +339,39 @@ gemm_f16_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
             sm += __shfl_xor(sm, 32);
             if (fh == 0 && row < ep.m_valid)
                 ep.lse_part[(size_t)row * ep.n_parts + slab] = make_float2(mx, sm);
+            if constexpr (EPI == EPI_LSE_TOPK) {
+                // The slab's best topk_k (logit, column) pairs of this row, best first: larger logit,
+                // then lower column.  The row's 64 logits are v[j][4g + e] of lanes `lane` and
+                // `lane ^ 32`, at column cbase + 32 j + 8 g + e: ascending with the register index, so
+                // the strict > of the in-lane scan keeps the lower column of equal logits.  One round
+                // per candidate: the lane's best, one exchange with the other half, and the winner's
+                // register set to -inf by the lane that holds it (every index static: no scratch).
+                // A round that finds only -inf (masked or taken columns) writes (-inf, INT_MAX).
+                float2* cq = ep.topk_cand + ((size_t)row * ep.n_parts + slab) * ep.topk_k;
+                for (int t = 0; t < ep.topk_k; ++t) {
+                    float bv = -INFINITY;
+                    int bc = 0x7fffffff;
+#pragma unroll
+                    for (int j = 0; j < TN; ++j)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r)
+                            if (v[j][r] > bv) {
+                                bv = v[j][r];
+                                bc = cbase + j * 32 + 8 * (r >> 2) + (r & 3);
+                            }
+                    const float pv = __shfl_xor(bv, 32);
+                    const int pc = __shfl_xor(bc, 32);
+                    const bool mine = bv > pv || (bv == pv && bc < pc);
+                    const float wv = mine ? bv : pv;
+                    const int wc = mine ? bc : pc;
+#pragma unroll
+                    for (int j = 0; j < TN; ++j)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r)
+                            if (cbase + j * 32 + 8 * (r >> 2) + (r & 3) == wc) v[j][r] = -INFINITY;
+                    if (fh == 0 && row < ep.m_valid) cq[t] = make_float2(wv, __int_as_float(wc));
+                }
+            }
         }
     } else {
         // Through LDS: each wave parks one 32-row slice of its accumulators (fp32, row
@@ -1756,7 +1790,8 @@ hipError_t launch_t(const f16* A, const f16* W, int M_pad, int N_pad, int K, con
 //   * the GELU three-part image of the K-concatenated fp16x3 form: the persistent kernel (P_X3IMG);
 //   * everything else (fp32 outputs, the residual epilogues, the decoder logsumexp): the pipelined
 //     256 x 256 (N % 256 == 0) or 256 x 128 kernel, 16x16x32 MFMA except the logsumexp epilogue
-//     (32x32x16), non-temporal stores for fp16 outputs (both decided inside gemm_f16_kernel).
+//     (32x32x16), non-temporal stores for fp16 outputs (both decided inside gemm_f16_kernel);
+//     EPI_LSE_TOPK is EPI_LSE on the same two tiles with the per-slab candidate selection added.
 // Measured-slower alternatives (tile configurations 2-7, 32x32x16 in the pipelined kernel, the
 // unstaggered persistent schedules, direct residual stores, ...) are recorded in profiles/r1_*;
 // their code paths were removed in round 4.
@@ -1878,6 +1913,9 @@ hipError_t launch_gemm(int epi, const f16* A, const f16* W, int M_pad, int N_pad
         case EPI_GELU_F32: return launch_epi<EPI_GELU_F32>(A, W, M_pad, N_pad, K, ep, st, tag);
         case EPI_RES_F32: return launch_epi<EPI_RES_F32>(A, W, M_pad, N_pad, K, ep, st, tag);
         case EPI_LSE: return launch_epi<EPI_LSE>(A, W, M_pad, N_pad, K, ep, st, tag);
+        case EPI_LSE_TOPK:
+            if (!ep.topk_cand || ep.topk_k < 1 || ep.topk_k > TOPK_MAX) return hipErrorInvalidValue;
+            return launch_epi<EPI_LSE_TOPK>(A, W, M_pad, N_pad, K, ep, st, tag);
         case EPI_BIAS_F32: return launch_epi<EPI_BIAS_F32>(A, W, M_pad, N_pad, K, ep, st, tag);
         case EPI_RESLN_F32: return launch_epi<EPI_RESLN_F32>(A, W, M_pad, N_pad, K, ep, st, tag);
     }

@@ -122,6 +122,12 @@ struct rs_model {
     DevBuf ctxq, resq, tq32, hq32, hq16, interq, lab, llog, part, rowlp_tmp;
     DevBuf meta;
     f16* emb_dst = nullptr;     // MODE_EMB output (rs_token_embed / rs_bertscore_recall)
+    // rs_masked_topk / rs_pll_topk (TopkCall): k != 0 makes head_mlm run the top-k decoder form into
+    // the call's outputs [sequence, k]; the candidate workspace exists from the first such call on
+    int topk_k = 0;
+    int32_t* topk_id = nullptr;
+    float* topk_lp = nullptr;
+    DevBuf topk_cand;           // topk_cand_bytes(vpad)
     DevBuf emb, plan;           // rs_bertscore_recall: token embeddings, work-item plan
     DevBuf flag;                // non-finite-output flag of the last scoring call(s) (range guard)
     bool sync_check = true;     // scoring calls synchronise and report their flags (rs_model_set_sync_check)
@@ -259,8 +265,9 @@ int report_flags(rs_model* m, hipStream_t st, const char* what) {
 // mode (default): the call waits for its stream and reports the flags.  Deferred mode
 // (rs_model_set_sync_check(m, 0)): the pass is only enqueued, the flags accumulate on the device
 // and rs_check reports them, so pipelined callers keep their stream asynchronous.
+// (mark_nonfinite: the pass alone, for a call with a second output to check.)
 template <class T>
-int check_finite(rs_model* m, hipStream_t st, const T* p, size_t n, const char* what) {
+int mark_nonfinite(rs_model* m, hipStream_t st, const T* p, size_t n) {
     if (!m->flag.p) {
         HIPTRY(m->flag.ensure(4));
         HIPTRY(hipMemset(m->flag.p, 0, 4));
@@ -270,6 +277,11 @@ int check_finite(rs_model* m, hipStream_t st, const T* p, size_t n, const char* 
         hipLaunchKernelGGL(nonfinite_kernel<T>, dim3(blocks), dim3(256), 0, st, p, n, m->flag.as<int>());
         HIPTRY(hipGetLastError());
     }
+    return RS_OK;
+}
+template <class T>
+int check_finite(rs_model* m, hipStream_t st, const T* p, size_t n, const char* what) {
+    if (int r = mark_nonfinite(m, st, p, n)) return r;
     if (!m->sync_check) return RS_OK;
     return report_flags(m, st, what);
 }
@@ -676,6 +688,17 @@ struct ChunkCtx {
         LAUNCH_OTHER(launch_ln_rows(tq, ns, m->gt, m->bet, eps, H, hq32, nullptr, hq16, kx, st));
         const MlmDecoder d{hq16, m->wdec, m->bdec, ns, m->vpad, cf.vocab, kx * H, d_tok, sm, c.s0, m->lab.as<int>(),
                            m->part.as<float2>(), m->llog.as<float>(), d_out_rows + c.s0};
+        if (m->topk_k) {
+            // the only fork of a top-k call: the decoder launcher (its GEMM runs in n_gemm sub-batches)
+            const int k = m->topk_k, n_gemm = (ns + TOPK_SUB_ROWS - 1) / TOPK_SUB_ROWS;
+            const MlmTopk t{k, m->topk_cand.as<float2>(), m->topk_id + (size_t)c.s0 * k, m->topk_lp + (size_t)c.s0 * k};
+            HIPTRY(launch_mlm_decoder_topk(d, t, st, [&](bool is_gemm, auto&& launch) {
+                ProfScope ps(m, st, is_gemm ? RS_K_DECODER : RS_K_OTHER,
+                             is_gemm ? 2.0 * ns * (double)cf.vocab * (kx * H) / n_gemm : 0);
+                return launch();
+            }));
+            return RS_OK;
+        }
         HIPTRY(launch_mlm_decoder(d, st, [&](bool is_gemm, auto&& launch) {
             ProfScope ps(m, st, is_gemm ? RS_K_DECODER : RS_K_OTHER, is_gemm ? 2.0 * ns * (double)cf.vocab * (kx * H) : 0);
             return launch();
@@ -826,6 +849,27 @@ int run_all(rs_model* m, hipStream_t st, const int* d_tok, SeqList& sl, int mode
     }
     return RS_OK;
 }
+
+// A top-k call: checks k and the outputs, makes sure of the candidate workspace and switches
+// head_mlm to the top-k decoder form until the call returns.
+struct TopkCall {
+    rs_model* m;
+    explicit TopkCall(rs_model* m_) : m(m_) {}
+    ~TopkCall() { m->topk_k = 0; m->topk_id = nullptr; m->topk_lp = nullptr; }
+    int begin(int k, int32_t* d_top_id, float* d_top_lp) {
+        if (!d_top_id || !d_top_lp) return fail(RS_EARG, "null argument");
+        if (k < 1 || k > RS_TOPK_MAX) return fail(RS_EARG, "k must be 1 .. RS_TOPK_MAX (16)");
+        if (k > m->cfg.vocab) return fail(RS_EARG, "k larger than the vocabulary");
+        if (int r = validate_call(m, MODE_MLM)) return r;
+        HIPTRY(hipSetDevice(m->device));
+        if (m->topk_cand.ensure(topk_cand_bytes(m->vpad)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(RS_ENOMEM, "top-k candidate workspace (" + std::to_string(topk_cand_bytes(m->vpad)) + " bytes)");
+        }
+        m->topk_k = k; m->topk_id = d_top_id; m->topk_lp = d_top_lp;
+        return RS_OK;
+    }
+};
 
 void prof_collect(rs_model* m) {
     if (m->recs.empty()) return;
@@ -1064,6 +1108,53 @@ int rs_masked_logprob(rs_model* m, const int32_t* d_ids, const int32_t* h_seq_of
     return check_finite(m, (hipStream_t)stream, d_out, (size_t)n_seq, "masked-token log-probability");
 }
 
+int rs_masked_topk(rs_model* m, const int32_t* d_ids, const int32_t* h_seq_off, const int32_t* h_query,
+                   int32_t n_seq, int32_t k, int32_t* d_top_id, float* d_top_lp, void* stream) {
+    if (!m || !h_seq_off || !h_query || n_seq < 0 || (n_seq > 0 && !d_ids)) return fail(RS_EARG, "null argument");
+    TopkCall tk(m);
+    if (int r = tk.begin(k, d_top_id, d_top_lp)) return r;
+    if (n_seq == 0) return RS_OK;
+    hipStream_t st = (hipStream_t)stream;
+    CALL_ORDER(m, st);
+    SeqList sl;
+    for (int s = 0; s < n_seq; ++s) {
+        const int o = h_seq_off[s], T = h_seq_off[s + 1] - o;
+        if (h_query[s] < 0 || h_query[s] >= T) return fail(RS_EARG, "query position outside its sequence");
+        sl.push(o, T, -1, h_query[s], 0);   // ids already masked by the caller; label column 0, its log-prob unused
+    }
+    HIPTRY(m->rowlp_tmp.ensure(sl.size() * 4));
+    if (int r = run_all(m, st, d_ids, sl, MODE_MLM, m->rowlp_tmp.as<float>(), nullptr, nullptr)) return r;
+    return check_finite(m, st, d_top_lp, (size_t)n_seq * k, "top-k log-probability");
+}
+
+int rs_pll_topk(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off, int32_t n_hyp, int32_t k,
+                double* d_pll, float* d_row_lp, int32_t* d_top_id, float* d_top_lp, void* stream) {
+    if (!m || !h_hyp_off || n_hyp < 0 || (n_hyp > 0 && !d_tok)) return fail(RS_EARG, "null argument");
+    TopkCall tk(m);
+    if (int r = tk.begin(k, d_top_id, d_top_lp)) return r;
+    if (n_hyp == 0) return RS_OK;
+    hipStream_t st = (hipStream_t)stream;
+    CALL_ORDER(m, st);
+    SeqList sl;
+    std::vector<int> hso(n_hyp + 1, 0);
+    for (int h = 0; h < n_hyp; ++h) {
+        const int o = h_hyp_off[h], T = h_hyp_off[h + 1] - o;
+        if (T < 3) return fail(RS_EARG, "hypothesis " + std::to_string(h) + " has no word (T < 3)");
+        for (int p = 1; p <= T - 2; ++p) sl.push(o, T, p, p, -1);   // the rows of rs_pll_score
+        hso[h + 1] = (int)sl.size();
+    }
+    float* rows = d_row_lp;
+    if (!rows) {
+        HIPTRY(m->rowlp_tmp.ensure(sl.size() * 4));
+        rows = m->rowlp_tmp.as<float>();
+    }
+    int* d_hso = nullptr;
+    if (int r = run_all(m, st, d_tok, sl, MODE_MLM, rows, &hso, &d_hso)) return r;
+    if (d_pll) LAUNCH_OTHER(launch_segsum_f64(rows, d_hso, n_hyp, d_pll, st));
+    if (int r = mark_nonfinite(m, st, rows, sl.size())) return r;
+    return check_finite(m, st, d_top_lp, sl.size() * k, "masked-token or top-k log-probability");
+}
+
 int rs_cls_score(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off, int32_t n_hyp,
                  float* d_out, void* stream) {
     if (!m || !h_hyp_off || n_hyp < 0 || (n_hyp > 0 && (!d_tok || !d_out))) return fail(RS_EARG, "null argument");
@@ -1190,7 +1281,7 @@ void rs_model_destroy(rs_model* m) {
     (void)hipDeviceSynchronize();
     for (void* p : m->allocs) (void)hipFree(p);
     for (DevBuf* b : {&m->xst, &m->xst1, &m->h16, &m->t32, &m->qkv, &m->ctx, &m->inter, &m->ctxq, &m->resq,
-                      &m->tq32, &m->hq32, &m->hq16, &m->interq, &m->lab, &m->llog, &m->part,
+                      &m->tq32, &m->hq32, &m->hq16, &m->interq, &m->lab, &m->llog, &m->part, &m->topk_cand,
                       &m->rowlp_tmp, &m->meta, &m->emb, &m->plan, &m->flag, &m->lnx, &m->lncnt,
                       &m->lnerr})
         b->release();

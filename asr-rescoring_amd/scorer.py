@@ -162,6 +162,45 @@ class PLLScorer(BertEngine):
                                               _lib.stream_ptr(self.device)))
         return out
 
+    def masked_topk(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, mask_pos, k: int = 5):
+        """The model's ``k`` preferred tokens at ``mask_pos`` of every row of a padded batch [B, T]
+        (the form ``masked_logprob`` takes): ``torch.topk(log_softmax(logits[range(B), mask_pos]), k)``
+        of MLM_PLL/main.py:101-105 without the [B, vocab] rows.  Returns device tensors
+        (ids int32 [B, k], logprob float32 [B, k]), best first, equal logits by the lower id."""
+        lens = _prefix_lengths(attention_mask)
+        B = input_ids.shape[0]
+        mp = np.asarray([int(x) for x in mask_pos], np.int32)
+        ids = input_ids.to(self.device)
+        T = ids.shape[1]
+        keep = (torch.arange(T, device=self.device)[None, :] < torch.from_numpy(lens).to(self.device)[:, None])
+        d_ids = ids[keep].to(torch.int32).contiguous()
+        off = np.zeros(B + 1, np.int32)
+        off[1:] = np.cumsum(lens)
+        top_id = torch.empty((B, max(int(k), 0)), dtype=torch.int32, device=self.device)
+        top_lp = torch.empty((B, max(int(k), 0)), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.rs_masked_topk(self.handle, _lib.ptr(d_ids), off.ctypes.data, mp.ctypes.data, B, int(k),
+                                           _lib.ptr(top_id), _lib.ptr(top_lp), _lib.stream_ptr(self.device)))
+        return top_id, top_lp
+
+    def topk_nbest(self, tokens, hyp_off, k: int = 5, return_pll: bool = False):
+        """``score_nbest`` plus the ``k`` preferred tokens of every masked row (rows ordered as
+        ``score_nbest(..., return_rows=True)``'s: hypothesis by hypothesis, position by position).
+
+        Returns (ids int32 [R, k], logprob float32 [R, k]) device tensors, followed by
+        (pll float64 [H], rows float32 [R]) — bitwise ``score_nbest``'s — when ``return_pll``."""
+        off = np.ascontiguousarray(hyp_off, np.int32)
+        n_hyp = len(off) - 1
+        d_tok = self._dev_tokens(tokens)
+        n_rows = int((np.diff(off) - 2).sum()) if n_hyp else 0
+        pll = torch.empty(n_hyp, dtype=torch.float64, device=self.device) if return_pll else None
+        rows = torch.empty(n_rows, dtype=torch.float32, device=self.device) if return_pll else None
+        top_id = torch.empty((n_rows, max(int(k), 0)), dtype=torch.int32, device=self.device)
+        top_lp = torch.empty((n_rows, max(int(k), 0)), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.rs_pll_topk(self.handle, _lib.ptr(d_tok), off.ctypes.data, n_hyp, int(k), _lib.ptr(pll),
+                                        _lib.ptr(rows), _lib.ptr(top_id), _lib.ptr(top_lp),
+                                        _lib.stream_ptr(self.device)))
+        return (top_id, top_lp, pll, rows) if return_pll else (top_id, top_lp)
+
     def row_logprobs(self, rows) -> torch.Tensor:
         """``token_score`` (MLM_PLL/main.py:101-105) of every do_job row, float32 [R] (device),
         all rows in one ragged launch sequence."""

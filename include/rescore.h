@@ -113,8 +113,8 @@ int rs_model_finalize(rs_model* m);
  * (>= 512).  Optional: scoring calls reserve a default on first use. */
 int rs_model_reserve(rs_model* m, int64_t max_rows);
 
-/* Range guard of the scoring calls (rs_pll_score, rs_masked_logprob, rs_cls_score,
- * rs_token_embed, rs_bertscore_recall): after the last launch the call checks its outputs
+/* Range guard of the scoring calls (rs_pll_score, rs_masked_logprob, rs_masked_topk, rs_pll_topk,
+ * rs_cls_score, rs_token_embed, rs_bertscore_recall): after the last launch the call checks its outputs
  * for non-finite values (an operand image that overflowed fp16 turns every dependent score
  * into inf / NaN), synchronises `stream` and returns RS_EUNSUP with a message instead of
  * handing back non-finite scores.  These calls therefore return with their work complete.
@@ -153,6 +153,35 @@ int rs_pll_score(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off, in
 int rs_masked_logprob(rs_model* m, const int32_t* d_ids, const int32_t* h_seq_off,
                       const int32_t* h_query, const int32_t* d_label, int32_t n_seq,
                       float* d_out, void* stream);
+
+/* Top-k token candidates at masked positions: the model's k preferred vocabulary entries of a row
+ * and their log-probabilities.  Reference seam: logits[range(B), mask_pos] of MLM_PLL/main.py:101-105
+ * BEFORE the label gather — the reference forms the whole [B, vocab] row and keeps one entry; these
+ * calls return the k best of log_softmax of that row (torch.topk order: best first) without ever
+ * materialising it: the decoder GEMM's epilogue keeps the best k (logit, column) pairs of every
+ * 64-column slab, and one merge per row orders them.
+ *   k          1 .. RS_TOPK_MAX, k <= vocab (else RS_EARG; a null output: RS_EARG)
+ *   d_top_id   int32   [rows, k] row-major   vocabulary ids, best first
+ *   d_top_lp   float32 [rows, k]             their log-probabilities, non-increasing along k
+ * Order: larger logit first; equal logits (fp32) by the lower id — a total order, so the result does
+ * not depend on chunking or tile shape and is bitwise reproducible (no atomics).  The log-prob of
+ * an id is formed from the same logit and the same logsumexp as rs_masked_logprob / rs_pll_score
+ * form for that id as a label: equal bit for bit.  Precision modes, chunking, layer-0 dedup and the
+ * last-layer query path are those of rs_pll_score; a model without the MLM head: RS_ESTATE.
+ * The range guard covers d_top_lp (and d_row_lp): a non-finite value is RS_EUNSUP, deferred by
+ * rs_model_set_sync_check(m, 0) like every scoring call's.
+ * Workspace: the first top-k call on a handle allocates the candidate buffer, 2048 rows x
+ * (vocab padded to 128) / 64 slabs x RS_TOPK_MAX x 8 bytes (bert-base-chinese: 87 MB), kept until
+ * rs_model_destroy; RS_ENOMEM if it does not fit.  The decoder of a top-k call runs over sub-batches
+ * of 2048 rows so that this size does not grow with max_rows; handles that never ask pay nothing. */
+#define RS_TOPK_MAX 16
+/* fill-mask on already-masked rows (arguments as rs_masked_logprob, no labels): rows = n_seq */
+int rs_masked_topk(rs_model* m, const int32_t* d_ids, const int32_t* h_seq_off, const int32_t* h_query,
+                   int32_t n_seq, int32_t k, int32_t* d_top_id, float* d_top_lp, void* stream);
+/* rs_pll_score plus the candidates of every masked row (rows ordered as d_row_lp: hypothesis by
+ * hypothesis, p = 1..L).  d_pll and d_row_lp (both nullable here) are rs_pll_score's, bit for bit. */
+int rs_pll_topk(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off, int32_t n_hyp, int32_t k,
+                double* d_pll, float* d_row_lp, int32_t* d_top_id, float* d_top_lp, void* stream);
 
 /* RescoreBert scoring (RescoreBert/model.py:13-21, RescoreBert/main.py:156-158):
  * CLS hidden of the last layer -> Linear(H, 1).  d_out float32 [n_hyp]. */
