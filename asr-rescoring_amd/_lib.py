@@ -59,6 +59,7 @@ _SIGS = {
     "rs_model_finalize": (ctypes.c_int, [P]),
     "rs_model_reserve": (ctypes.c_int, [P, I64]),
     "rs_pll_score": (ctypes.c_int, [P, P, P, I32, P, P, P]),
+    "rs_pll_score_spans": (ctypes.c_int, [P, P, P, I32, P, P, P, P, P, P, P]),
     "rs_masked_logprob": (ctypes.c_int, [P, P, P, P, P, I32, P, P]),
     "rs_masked_topk": (ctypes.c_int, [P, P, P, P, I32, I32, P, P, P]),
     "rs_pll_topk": (ctypes.c_int, [P, P, P, I32, I32, P, P, P, P, P]),
@@ -93,6 +94,7 @@ _SIGS = {
     "rs_vocab_load": (P, [ctypes.c_char_p]),
     "rs_vocab_size": (ctypes.c_int, [P]),
     "rs_vocab_free": (None, [P]),
+    "rs_vocab_continuation": (ctypes.c_int, [P, P, I64, P]),
     "rs_tokenize_batch": (I64, [P, ctypes.POINTER(ctypes.c_char_p), I32, I32, P, I64, P]),
     "rs_json_write_scores": (ctypes.c_int, [ctypes.c_char_p, I32, ctypes.POINTER(ctypes.c_char_p), P,
                                             ctypes.POINTER(ctypes.c_char_p), P]),

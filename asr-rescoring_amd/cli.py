@@ -15,7 +15,7 @@ generator when ``random_init_seed`` is set.  The tokenizer is ``BertTokenizer``-
 per-character for CJK (``data.CharTokenizer``) built from the data, unless ``model.vocab``
 names a ``vocab.txt`` — then the native BertTokenizer-compatible ``frontend.NativeTokenizer``
 (and score JSON is written by the native ``frontend.json_saving``).  Extra keys: ``precision`` (fp16 / fp16x3), ``max_rows``,
-``mode`` (rescore fusion formula: norm / legacy / am_norm).
+``mode`` (rescore fusion formula: norm / legacy / am_norm), ``pll_variant`` (mlm_pll: original / word_l2r / whole_word).
 """
 from __future__ import annotations
 
@@ -77,16 +77,32 @@ def _nbest_tokens(hyps_text: Dict[str, Dict[str, str]], tok, max_utt=1 << 30, n_
     return D.from_lists(words), keys
 
 
+def _pll_variant(cfg) -> str:
+    v = str(get(cfg, "pll_variant", "original"))
+    if v not in D.PLL_VARIANTS:
+        raise ValueError(f"unknown pll_variant {v!r} {D.PLL_VARIANTS}")
+    return v
+
+
 # --------------------------------------------------------------------------------------
 def mlm_pll(cfg) -> Dict[str, str]:
     """MLM_PLL/main.py:164-203 (pll_bert_scoring).  Accepts the reference's preprocessed
-    rows (``*_data_path``: do_job output) or raw ``*_hyps_text_path`` JSON.
+    rows (``*_data_path``: do_job output) or raw ``*_hyps_text_path`` JSON.  Extra key
+    ``pll_variant`` (text inputs only): ``original`` (default), ``word_l2r`` or ``whole_word`` (Kauf &
+    Ivanova 2023; ``data.pll_spans`` over the word boundaries of the native tokenizer's WordPiece output).
 
     Launched with torchrun (WORLD_SIZE > 1): one process per GPU, each scores a contiguous,
     cost-balanced utterance range (``shard.plan_shards``); the scores meet in one all-gather
     (RCCL) and rank 0 writes the JSON (the reference is single-process)."""
     from . import shard
     from .scorer import PLLScorer
+    variant, noted = _pll_variant(cfg), False
+    if variant != "original":
+        for split in ("train", "dev", "test"):
+            rows_path = get(cfg, f"{split}_data_path")
+            if rows_path and os.path.exists(rows_path):
+                raise ValueError(f"pll_variant {variant!r} needs {split}_hyps_text_path: the rows of "
+                                 f"{split}_data_path are already masked one position each")
     rank, world, local = shard.init_from_env()
     device = local if world > 1 else _dev(cfg)
     scorer = PLLScorer(_weights(cfg, "mlm"), BERT_BASE, device=device, max_rows=get(cfg, "max_rows", 65536),
@@ -102,7 +118,17 @@ def mlm_pll(cfg) -> Dict[str, str]:
             hyps = _load(text_path)
             tok = _tokenizer(cfg, [t for h in hyps.values() for t in h.values()])
             nb, keys = _nbest_tokens(hyps, tok)
-            both = shard.score_sharded(nb, lambda sub: scorer.score_nbest(sub.tokens, sub.hyp_off))
+            use = variant
+            if variant != "original" and not hasattr(tok, "word_starts"):
+                if not noted:
+                    print(f"mlm_pll: pll_variant {variant} without model.vocab: the per-character tokenizer makes "
+                          "every token a word, so the scores are those of pll_variant original", file=sys.stderr)
+                    noted = True
+                use = "original"
+            if use != "original":
+                nb.word_start = tok.word_starts(nb.tokens)
+            both = shard.score_sharded(nb, lambda sub: scorer.score_nbest(sub.tokens, sub.hyp_off, variant=use,
+                                                                          word_start=sub.word_start))
             pll = both[1].cpu().numpy()
             output_score = {}
             for (u, h), s in zip(keys, pll):

@@ -139,12 +139,13 @@ __device__ __forceinline__ float4 il_load4(const f16* row, int c) {
 struct SeqMeta {
     const int* tok_off;    // offset of the sequence's [CLS] in the token buffer
     const int* len;        // T
-    const int* mask_pos;   // position replaced by [MASK] on device, -1 = none
+    const int* mask_pos;   // first position replaced by [MASK] on device, -1 = none
     const int* query;      // row whose last-layer state is scored
     const int* label;      // label id at query, -1 = take tokens[tok_off + query]
     const int* row;        // first token row of the sequence (global row index)
     const int* urow_h;     // layer-0 dedup: first unique row of the sequence's hypothesis (chunk-local)
-    const int* urow_m;     // layer-0 dedup: the sequence's [MASK] unique row (chunk-local)
+    const int* urow_m;     // layer-0 dedup: the unique row of the sequence's first [MASK] position (chunk-local)
+    const int* mask_end;   // end of the [MASK] span [mask_pos, mask_end); -1 = none
 };
 
 __device__ __forceinline__ float wave_sum(float v) {
@@ -212,9 +213,10 @@ hipError_t launch_ln_res32(float* x32, const float2* stats, float2* stats_out, c
                            int kx, hipStream_t st);
 hipError_t launch_ln_res_img(f16* h16, const float* o32, int rows, const float* g, const float* b, float eps, int H,
                              hipStream_t st);
-// Unique layer-0 rows (dedup): for every hypothesis of the chunk its T rows, and every
-// sequence's [MASK] row, as the fp16 operand image of LN(embedding) (rows of SeqMeta.urow_*)
-hipError_t launch_embed_unique(const int* tok, SeqMeta sm, int s0, int s1, int mask_id, int vocab,
+// Unique layer-0 rows (dedup): the urows rows of the chunk's plan (seq_plan.h: per run of copies of
+// a hypothesis its T rows, then the [MASK] rows of the run's masked range), as the fp16 operand
+// image of LN(embedding) (rows of SeqMeta.urow_*)
+hipError_t launch_embed_unique(const int* tok, SeqMeta sm, int s0, int s1, int urows, int mask_id, int vocab,
                                const float* word, const float* pos, const float* type0, const float* g,
                                const float* b, float eps, int H, f16* h16u, int kx, hipStream_t st);
 // BERTScore recall matrix (k_bertscore.hip); items = (utterance, j0, j1, -) ref-column runs of
@@ -231,7 +233,8 @@ hipError_t launch_embed_out(const float* x32, const float2* stats, const float* 
 // H == 64 heads.  max_len > 0: longest sequence of the launch; it and (qkv32, dedup) choose the
 // kernel (table in k_attn.hip): the 16x16x32 kernels serve launches whose sequences all fit one
 // 64-key block, the 32x32x16 kernel the others (fewer K/V reloads).
-// dedup: qkv holds unique rows; sequence s, position t reads row (t == mask_pos ? urow_m : urow_h + t)
+// dedup: qkv holds unique rows; sequence s, position t reads row
+// (mask_pos <= t < mask_end ? urow_m + (t - mask_pos) : urow_h + t)
 hipError_t launch_attention_full(const void* qkv, bool qkv32, SeqMeta sm, int s0, int s1, int row0,
                                  int H, int heads, f16* ctx, int kx, hipStream_t st, bool dedup, int max_len);
 // resq = LN(x32[query row]) (x32 pre-LN, with its row statistics and LN weight / bias)

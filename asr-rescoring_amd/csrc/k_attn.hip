@@ -40,23 +40,25 @@ __device__ __forceinline__ half4 tr_read(const f16* p) {
 
 // Q/K/V row of position t of sequence s, head hd: rowp(t) points at the head's 64 Q columns
 // of a [rows, ld = 3H] buffer (K at + H, V at + 2H).  rs: the sequence's first row.
-// DEDUP (layer 0): qkv holds the chunk's unique rows; position t reads row urow_m[s] when t
-// is the sequence's masked position (the masked copy's [MASK] row lives apart from its
-// hypothesis' rows), urow_h[s] + t otherwise.
+// DEDUP (layer 0): qkv holds the chunk's unique rows; position t reads row urow_m[s] + (t - lo)
+// when it lies in the sequence's masked span [lo, hi) (the [MASK] rows of a hypothesis live apart
+// from its unmasked rows), urow_h[s] + t otherwise.  Both are `row origin + t`: the span only
+// chooses the origin (urow_m - lo or urow_h).
 template <class QT, bool DEDUP>
 struct SeqRows {
     const QT* base;
-    const QT* mbase;
-    int ld, mp;
+    const QT* mbase;           // origin of the span's rows: row urow_m - lo (only positions >= lo read it)
+    int ld, lo, n;
     __device__ __forceinline__ SeqRows(const QT* qkv, const SeqMeta& sm, int s, int rs, int ld_, int hd) : ld(ld_) {
         const int ub = DEDUP ? sm.urow_h[s] : rs;
-        mp = DEDUP ? sm.mask_pos[s] : -1;
-        const int um = DEDUP ? sm.urow_m[s] : 0;
+        lo = DEDUP ? sm.mask_pos[s] : 0;
+        n = DEDUP ? sm.mask_end[s] - lo : 0;
+        const int um = DEDUP ? sm.urow_m[s] - lo : 0;
         base = qkv + (size_t)ub * ld + hd * 64;
-        mbase = qkv + (size_t)um * ld + hd * 64;
+        mbase = qkv + (ptrdiff_t)um * ld + hd * 64;
     }
     __device__ __forceinline__ const QT* operator()(int t) const {
-        if constexpr (DEDUP) return t == mp ? mbase : base + (size_t)t * ld;
+        if constexpr (DEDUP) return ((unsigned)(t - lo) < (unsigned)n ? mbase : base) + (size_t)t * ld;
         else return base + (size_t)t * ld;
     }
 };

@@ -16,6 +16,7 @@
 // rebuild LN(x) with ln_apply, so no LN kernel writes an fp32 copy of its output.
 #include <type_traits>
 #include "common.h"
+#include "seq_plan.h"
 
 namespace {
 
@@ -53,14 +54,14 @@ __device__ __forceinline__ void ln_store(const float4 (&x)[NV], const float* g, 
     }
 }
 
-// Embedding sum of position t of a sequence (token t, or [MASK] when t == mp): the one
+// Embedding sum of position t of a sequence (token t, or [MASK] when lo <= t < hi): the one
 // expression both the copy-row and the unique-row kernels use (bit-identical rows).
 template <int NV>
-__device__ __forceinline__ void embed_row(const int* tok, int toff, int t, int mp, int mask_id, int vocab,
+__device__ __forceinline__ void embed_row(const int* tok, int toff, int t, int lo, int hi, int mask_id, int vocab,
                                           const float* word, const float* pos, const float* type0, int lane,
                                           float4 (&x)[NV]) {
     constexpr int H = NV * 256;
-    int id = (t == mp) ? mask_id : tok[toff + t];
+    int id = (t >= lo && t < hi) ? mask_id : tok[toff + t];
     id = min(max(id, 0), vocab - 1);              // out-of-range ids are clamped, never read OOB
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
@@ -73,26 +74,29 @@ __device__ __forceinline__ void embed_row(const int* tok, int toff, int t, int m
     }
 }
 
-// Layer-0 dedup: block s writes the [MASK] unique row of sequence s, and — when s is the
-// first copy of its hypothesis in the chunk — the hypothesis' T unmasked unique rows.
+// Layer-0 dedup: the unique rows of the chunk's plan (seq_plan.h plan_unique_rows), each written
+// by exactly one block (unique_rows_owned): the first copy of a run writes the hypothesis' T
+// unmasked rows, the last copy the run's [MASK] rows.  s1 - s0 blocks; urows: the chunk's count.
 template <int NV>
 __global__ void __launch_bounds__(256)
-embed_unique_kernel(const int* __restrict__ tok, SeqMeta sm, int s0, int mask_id, int vocab,
+embed_unique_kernel(const int* __restrict__ tok, SeqMeta sm, int s0, int urows, int mask_id, int vocab,
                     const float* __restrict__ word, const float* __restrict__ pos,
                     const float* __restrict__ type0, const float* __restrict__ g,
                     const float* __restrict__ b, float eps, f16* __restrict__ h16u, int kx) {
     constexpr int H = NV * 256;
     const int s = s0 + blockIdx.x;
-    const int T = sm.len[s], toff = sm.tok_off[s], mp = sm.mask_pos[s];
+    const int T = sm.len[s], toff = sm.tok_off[s], uh = sm.urow_h[s];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const bool first = blockIdx.x == 0 || sm.urow_h[s - 1] != sm.urow_h[s];
-    const int n = first ? T + 1 : 1;
-    for (int k = wave; k < n; k += 4) {
-        const bool masked = k == T || !first;
-        const int t = masked ? mp : k;
-        const size_t r = masked ? (size_t)sm.urow_m[s] : (size_t)(sm.urow_h[s] + k);
+    const bool first = blockIdx.x == 0, last = blockIdx.x == gridDim.x - 1;
+    const UniqueOwn w = unique_rows_owned(first, last, first ? 0 : sm.urow_h[s - 1], uh, last ? 0 : sm.urow_h[s + 1],
+                                          sm.urow_m[s], T, sm.mask_pos[s], urows);
+    for (int k = wave; k < w.n_orig + w.n_mask; k += 4) {
+        const bool masked = k >= w.n_orig;
+        const int j = k - w.n_orig;
+        const int t = masked ? w.mask_pos + j : k;
+        const size_t r = masked ? (size_t)(w.mask_row + j) : (size_t)(uh + k);
         float4 x[NV];
-        embed_row<NV>(tok, toff, t, masked ? t : -1, mask_id, vocab, word, pos, type0, lane, x);
+        embed_row<NV>(tok, toff, t, masked ? t : -1, masked ? t + 1 : -1, mask_id, vocab, word, pos, type0, lane, x);
         ln_store<NV>(x, g, b, eps, lane, nullptr, nullptr, h16u + r * kx * H, kx);
     }
 }
@@ -106,12 +110,12 @@ embed_ln_kernel(const int* __restrict__ tok, SeqMeta sm, int s0, int row0, int m
                 float2* __restrict__ stats, f16* __restrict__ h16, int kx) {
     constexpr int H = NV * 256;
     const int s = s0 + blockIdx.x;
-    const int T = sm.len[s], toff = sm.tok_off[s], mp = sm.mask_pos[s];
+    const int T = sm.len[s], toff = sm.tok_off[s], lo = sm.mask_pos[s], hi = sm.mask_end[s];
     const int rs = sm.row[s] - row0;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int t = wave; t < T; t += 4) {
         float4 x[NV];
-        embed_row<NV>(tok, toff, t, mp, mask_id, vocab, word, pos, type0, lane, x);
+        embed_row<NV>(tok, toff, t, lo, hi, mask_id, vocab, word, pos, type0, lane, x);
         const size_t r = (size_t)(rs + t);
 #pragma unroll
         for (int v = 0; v < NV; ++v) if (x32) *(float4*)(x32 + r * H + v * 256 + lane * 4) = x[v];
@@ -455,14 +459,14 @@ hipError_t launch_embed_ln(const int* tok, SeqMeta sm, int s0, int s1, int row0,
     });
 }
 
-hipError_t launch_embed_unique(const int* tok, SeqMeta sm, int s0, int s1, int mask_id, int vocab,
+hipError_t launch_embed_unique(const int* tok, SeqMeta sm, int s0, int s1, int urows, int mask_id, int vocab,
                                const float* word, const float* pos, const float* type0, const float* g,
                                const float* b, float eps, int H, f16* h16u, int kx, hipStream_t st) {
     const int n = s1 - s0;
     if (n <= 0) return hipSuccess;
     return launch_for_h(H, [&](auto nv) {
-        hipLaunchKernelGGL(embed_unique_kernel<decltype(nv)::value>, dim3(n), dim3(256), 0, st, tok, sm, s0, mask_id,
-                           vocab, word, pos, type0, g, b, eps, h16u, kx);
+        hipLaunchKernelGGL(embed_unique_kernel<decltype(nv)::value>, dim3(n), dim3(256), 0, st, tok, sm, s0, urows,
+                           mask_id, vocab, word, pos, type0, g, b, eps, h16u, kx);
     });
 }
 

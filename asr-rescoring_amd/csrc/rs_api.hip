@@ -14,6 +14,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "seq_plan.h"
 #include "../../include/rescore.h"
 
 namespace {
@@ -57,12 +58,6 @@ struct Layer {
     f16 *iqkv = nullptr, *io = nullptr, *i1 = nullptr, *i2 = nullptr;   // fp16x3: interleaved two-part
                                     // images [W_hi | W_lo*64] of the split-operand GEMMs (ldw = 2K)
     float *bqkv, *bo, *b1, *b2, *g1, *be1, *g2, *be2;
-};
-
-struct Chunk {
-    int s0, s1, rows;
-    int urows = 0;     // layer-0 unique rows (dedup mode), 0 = dedup off for this chunk
-    int max_len = 0;   // longest sequence of the chunk (attention kernel choice)
 };
 
 // Pinned staging buffer (int words) of one asynchronous upload per call: the next call waits for
@@ -568,7 +563,7 @@ struct ChunkCtx {
                                eps, H, o.imgres ? nullptr : t32, o.imgres ? nullptr : xst, dedup && !o.x3s ? nullptr : h16,
                                kxf, st));
         if (dedup)
-            HIPTRY(launch_embed_unique(d_tok, sm, c.s0, c.s1, cf.mask_id, cf.vocab, m->word32, m->pos32, m->type32,
+            HIPTRY(launch_embed_unique(d_tok, sm, c.s0, c.s1, c.urows, cf.mask_id, cf.vocab, m->word32, m->pos32, m->type32,
                                        m->eg, m->eb, eps, H, o.x3s ? inter : h16, kxf, st));
         return RS_OK;
     }
@@ -729,35 +724,6 @@ struct ChunkCtx {
     }
 };
 
-// Host-side sequence list (structure of arrays) for one call.
-struct SeqList {
-    std::vector<int> tok_off, len, mask, query, label, row, urow_h, urow_m;
-    void push(int to, int T, int mp, int q, int lb) {
-        tok_off.push_back(to); len.push_back(T); mask.push_back(mp); query.push_back(q);
-        label.push_back(lb); row.push_back(0); urow_h.push_back(0); urow_m.push_back(0);
-    }
-    size_t size() const { return len.size(); }
-};
-
-// Layer-0 dedup (MLM_PLL): the masked copies of one hypothesis share every layer-0 input row
-// except the masked one, so the layer-0 QKV projection runs over UNIQUE rows: per hypothesis
-// (within a chunk) its T original rows, then one [MASK] row per copy.  urow_h[s] = first
-// unique row of the hypothesis, urow_m[s] = the copy's masked row (chunk-local).  Returns the
-// chunk's unique-row count, or 0 when a sequence has no mask position (dedup not applicable).
-int plan_unique_rows(SeqList& sl, int s0, int s1) {
-    int u = 0, base = 0;
-    for (int s = s0; s < s1; ++s) {
-        if (sl.mask[s] < 0) return 0;
-        if (s == s0 || sl.tok_off[s] != sl.tok_off[s - 1] || sl.len[s] != sl.len[s - 1]) {
-            base = u;
-            u += sl.len[s];
-        }
-        sl.urow_h[s] = base;
-        sl.urow_m[s] = u++;
-    }
-    return u;
-}
-
 int validate_call(const rs_model* m, int mode) {
     if (!m->finalized) return fail(RS_ESTATE, "rs_model_finalize not called");
     if (mode == MODE_MLM && !(m->cfg.heads_mask & RS_HEAD_MLM)) return fail(RS_ESTATE, "model has no MLM head");
@@ -781,50 +747,40 @@ int64_t chunk_cap(const rs_model* m, const CallOpts& o) {
 
 // Chunks of <= cap rows and <= s_cap sequences; sets sl.row (first row of a sequence in its chunk).
 int cut_chunks(const rs_model* m, SeqList& sl, int64_t cap, std::vector<Chunk>* chunks) {
-    const size_t S = sl.size();
-    int rows = 0, s0 = 0, max_len = 0;
-    for (size_t s = 0; s < S; ++s) {
-        const int T = sl.len[s];
+    for (int T : sl.len) {
         if (T > m->cfg.max_pos) return fail(RS_EUNSUP, "sequence longer than max_position_embeddings");
         if (T < 1) return fail(RS_EARG, "empty sequence");
         if (T > m->max_rows) return fail(RS_EARG, "sequence longer than the reserved rows");
-        if (rows + T > cap || (int)s - s0 >= m->s_cap) {
-            chunks->push_back({s0, (int)s, rows, 0, max_len});
-            s0 = (int)s;
-            rows = 0;
-            max_len = 0;
-        }
-        sl.row[s] = rows;
-        rows += T;
-        max_len = std::max(max_len, T);
     }
-    if (S) chunks->push_back({s0, (int)S, rows, 0, max_len});
+    cut_rows(sl, cap, m->s_cap, chunks);
     return RS_OK;
 }
 
-// Layer-0 dedup plan (plan_unique_rows) of every chunk it applies to (call_opts: RS_DEDUP, x3_dedup).
+// Layer-0 dedup plan (seq_plan.h plan_unique_rows) of every chunk it applies to (call_opts: RS_DEDUP,
+// x3_dedup) and whose unique rows fit the reserved rows (unique_rows_fit; else the chunk runs plain).
 void plan_dedup(const rs_model* m, const CallOpts& o, int mode, SeqList& sl, std::vector<Chunk>& chunks) {
     if (!(o.dedup && mode == MODE_MLM && (m->kx == 1 || o.x3_dedup) && m->cfg.layers >= 2)) return;
     for (Chunk& c : chunks)
-        if (m->kx == 1 || c.max_len <= 64) c.urows = plan_unique_rows(sl, c.s0, c.s1);
+        if (m->kx == 1 || c.max_len <= 64)
+            c.urows = unique_rows_fit(plan_unique_rows(sl, c.s0, c.s1), gemm_row_align(), m->m_pad);
 }
 
-// One upload of all metadata through the pinned staging buffer: the eight SeqList columns, then
+// One upload of all metadata through the pinned staging buffer: the nine SeqList columns, then
 // the extra ints (e.g. hypothesis -> sequence offsets; *d_extra); d_label: device labels instead.
 int upload_meta(rs_model* m, hipStream_t st, const SeqList& sl, const std::vector<int>* extra, const int* d_label,
                 SeqMeta* sm, int** d_extra) {
-    const size_t S = sl.size(), n_extra = extra ? extra->size() : 0, n_int = 8 * S + n_extra;
+    const size_t S = sl.size(), n_extra = extra ? extra->size() : 0, n_int = 9 * S + n_extra;
     HIPTRY(m->stage_meta.begin(n_int));
     int* p = m->stage_meta.p;
-    const std::vector<int>* cols[8] = {&sl.tok_off, &sl.len, &sl.mask, &sl.query, &sl.label, &sl.row,
-                                       &sl.urow_h, &sl.urow_m};
-    for (int k = 0; k < 8; ++k) std::memcpy(p + k * S, cols[k]->data(), S * 4);
-    if (n_extra) std::memcpy(p + 8 * S, extra->data(), n_extra * 4);
+    const std::vector<int>* cols[9] = {&sl.tok_off, &sl.len, &sl.mask, &sl.query, &sl.label, &sl.row,
+                                       &sl.urow_h, &sl.urow_m, &sl.mask_end};
+    for (int k = 0; k < 9; ++k) std::memcpy(p + k * S, cols[k]->data(), S * 4);
+    if (n_extra) std::memcpy(p + 9 * S, extra->data(), n_extra * 4);
     HIPTRY(m->stage_meta.upload(m->meta, n_int, st));
     int* d = m->meta.as<int>();
     if (d_label) HIPTRY(hipMemcpyAsync(d + 4 * S, d_label, S * 4, hipMemcpyDeviceToDevice, st));
-    *sm = SeqMeta{d, d + S, d + 2 * S, d + 3 * S, d + 4 * S, d + 5 * S, d + 6 * S, d + 7 * S};
-    if (d_extra) *d_extra = d + 8 * S;
+    *sm = SeqMeta{d, d + S, d + 2 * S, d + 3 * S, d + 4 * S, d + 5 * S, d + 6 * S, d + 7 * S, d + 8 * S};
+    if (d_extra) *d_extra = d + 9 * S;
     return RS_OK;
 }
 
@@ -1077,12 +1033,48 @@ int rs_pll_score(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off, in
     for (int h = 0; h < n_hyp; ++h) {
         const int o = h_hyp_off[h], T = h_hyp_off[h + 1] - o;
         if (T < 3) return fail(RS_EARG, "hypothesis " + std::to_string(h) + " has no word (T < 3)");
-        for (int p = 1; p <= T - 2; ++p) sl.push(o, T, p, p, -1);   // do_job rows, p = mask_pos
+        for (int p = 1; p <= T - 2; ++p) sl.push(o, T, p, p + 1, p, -1);   // do_job rows, p = mask_pos
         hso[h + 1] = (int)sl.size();
     }
     float* rows = d_row_lp;
     if (!rows) {
         HIPTRY(m->rowlp_tmp.ensure(sl.size() * 4));
+        rows = m->rowlp_tmp.as<float>();
+    }
+    int* d_hso = nullptr;
+    if (int r = run_all(m, st, d_tok, sl, MODE_MLM, rows, &hso, &d_hso)) return r;
+    LAUNCH_OTHER(launch_segsum_f64(rows, d_hso, n_hyp, d_pll, st));
+    return check_finite(m, st, rows, sl.size(), "masked-token log-probability");
+}
+
+int rs_pll_score_spans(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off, int32_t n_hyp,
+                       const int32_t* h_row_off, const int32_t* h_lo, const int32_t* h_hi, const int32_t* h_query,
+                       double* d_pll, float* d_row_lp, void* stream) {
+    if (!m || !h_hyp_off || !h_row_off || n_hyp < 0 || (n_hyp > 0 && (!d_tok || !d_pll)))
+        return fail(RS_EARG, "null argument");
+    hipStream_t st = (hipStream_t)stream;
+    if (n_hyp == 0) return RS_OK;
+    if (h_row_off[0] != 0) return fail(RS_EARG, "row_off[0] must be 0");
+    for (int h = 0; h < n_hyp; ++h)
+        if (h_row_off[h + 1] < h_row_off[h]) return fail(RS_EARG, "row_off not ascending at hypothesis " + std::to_string(h));
+    if (h_row_off[n_hyp] > 0 && (!h_lo || !h_hi || !h_query)) return fail(RS_EARG, "null argument");
+    CALL_ORDER(m, st);
+    SeqList sl;
+    std::vector<int> hso(h_row_off, h_row_off + n_hyp + 1);     // one sequence per row
+    for (int h = 0; h < n_hyp; ++h) {
+        const int o = h_hyp_off[h], T = h_hyp_off[h + 1] - o;
+        for (int r = h_row_off[h]; r < h_row_off[h + 1]; ++r) {
+            if (!span_ok(T, h_lo[r], h_hi[r], h_query[r]))
+                return fail(RS_EARG, "row " + std::to_string(r) + " (hypothesis " + std::to_string(h) + ", T = " +
+                                         std::to_string(T) + "): need 1 <= lo <= query < hi <= T - 1, got lo " +
+                                         std::to_string(h_lo[r]) + ", hi " + std::to_string(h_hi[r]) + ", query " +
+                                         std::to_string(h_query[r]));
+            sl.push(o, T, h_lo[r], h_hi[r], h_query[r], -1);
+        }
+    }
+    float* rows = d_row_lp;
+    if (!rows) {
+        HIPTRY(m->rowlp_tmp.ensure(std::max<size_t>(sl.size(), 1) * 4));
         rows = m->rowlp_tmp.as<float>();
     }
     int* d_hso = nullptr;
@@ -1102,7 +1094,7 @@ int rs_masked_logprob(rs_model* m, const int32_t* d_ids, const int32_t* h_seq_of
     for (int s = 0; s < n_seq; ++s) {
         const int o = h_seq_off[s], T = h_seq_off[s + 1] - o;
         if (h_query[s] < 0 || h_query[s] >= T) return fail(RS_EARG, "query position outside its sequence");
-        sl.push(o, T, -1, h_query[s], 0);   // ids already masked by the caller
+        sl.push(o, T, -1, -1, h_query[s], 0);   // ids already masked by the caller
     }
     if (int r = run_all(m, (hipStream_t)stream, d_ids, sl, MODE_MLM, d_out, nullptr, nullptr, d_label)) return r;
     return check_finite(m, (hipStream_t)stream, d_out, (size_t)n_seq, "masked-token log-probability");
@@ -1120,7 +1112,7 @@ int rs_masked_topk(rs_model* m, const int32_t* d_ids, const int32_t* h_seq_off, 
     for (int s = 0; s < n_seq; ++s) {
         const int o = h_seq_off[s], T = h_seq_off[s + 1] - o;
         if (h_query[s] < 0 || h_query[s] >= T) return fail(RS_EARG, "query position outside its sequence");
-        sl.push(o, T, -1, h_query[s], 0);   // ids already masked by the caller; label column 0, its log-prob unused
+        sl.push(o, T, -1, -1, h_query[s], 0);   // ids already masked by the caller; label column 0, its log-prob unused
     }
     HIPTRY(m->rowlp_tmp.ensure(sl.size() * 4));
     if (int r = run_all(m, st, d_ids, sl, MODE_MLM, m->rowlp_tmp.as<float>(), nullptr, nullptr)) return r;
@@ -1140,7 +1132,7 @@ int rs_pll_topk(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off, int
     for (int h = 0; h < n_hyp; ++h) {
         const int o = h_hyp_off[h], T = h_hyp_off[h + 1] - o;
         if (T < 3) return fail(RS_EARG, "hypothesis " + std::to_string(h) + " has no word (T < 3)");
-        for (int p = 1; p <= T - 2; ++p) sl.push(o, T, p, p, -1);   // the rows of rs_pll_score
+        for (int p = 1; p <= T - 2; ++p) sl.push(o, T, p, p + 1, p, -1);   // the rows of rs_pll_score
         hso[h + 1] = (int)sl.size();
     }
     float* rows = d_row_lp;
@@ -1164,7 +1156,7 @@ int rs_cls_score(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off, in
     for (int h = 0; h < n_hyp; ++h) {
         const int o = h_hyp_off[h], T = h_hyp_off[h + 1] - o;
         if (T < 1) return fail(RS_EARG, "empty hypothesis");
-        sl.push(o, T, -1, 0, 0);      // query = [CLS] (RescoreBert/model.py:19)
+        sl.push(o, T, -1, -1, 0, 0);      // query = [CLS] (RescoreBert/model.py:19)
     }
     if (int r = run_all(m, (hipStream_t)stream, d_tok, sl, MODE_CLS, d_out, nullptr, nullptr)) return r;
     return check_finite(m, (hipStream_t)stream, d_out, (size_t)n_hyp, "RescoreBert score");
@@ -1179,7 +1171,7 @@ int rs_token_embed(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off, 
     for (int h = 0; h < n_hyp; ++h) {
         const int o = h_hyp_off[h], T = h_hyp_off[h + 1] - o;
         if (o < 0 || T < 1) return fail(RS_EARG, "hypothesis " + std::to_string(h) + " is empty");
-        sl.push(o, T, -1, 0, 0);
+        sl.push(o, T, -1, -1, 0, 0);
     }
     m->emb_dst = (f16*)d_emb;
     const int r = run_all(m, (hipStream_t)stream, d_tok, sl, MODE_EMB, nullptr, nullptr, nullptr);

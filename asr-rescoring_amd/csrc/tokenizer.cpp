@@ -109,6 +109,7 @@ struct Vocab {
     std::unordered_map<std::string, int> ids;
     int unk = 0, cls = 101, sep = 102;
     int size = 0;
+    std::vector<bool> cont;          // by id: the entry starts with "##" (a WordPiece continuation piece)
 };
 
 // lower-case then accent-strip one token (BasicTokenizer: token.lower(), _run_strip_accents)
@@ -312,6 +313,7 @@ void* rs_vocab_load(const char* path) {
     int idx = 0;
     while (std::getline(f, line)) {                 // token = line.rstrip("\n")
         v->ids[line] = idx++;
+        v->cont.push_back(line.size() >= 2 && line[0] == '#' && line[1] == '#');
     }
     v->size = idx;
     auto get = [&](const char* t, int dflt) {
@@ -327,6 +329,15 @@ void* rs_vocab_load(const char* path) {
 int rs_vocab_size(const void* vocab) { return vocab ? ((const Vocab*)vocab)->size : -1; }
 
 void rs_vocab_free(void* vocab) { delete (Vocab*)vocab; }
+
+// out[i] = 1 where the vocabulary entry of ids[i] starts with "##" (the piece continues a word),
+// 0 otherwise, ids outside [0, size) included.
+int rs_vocab_continuation(const void* vocab, const int32_t* ids, int64_t n, uint8_t* out) {
+    if (!vocab || n < 0 || (n > 0 && (!ids || !out))) return -1;
+    const Vocab& v = *(const Vocab*)vocab;
+    for (int64_t i = 0; i < n; ++i) out[i] = ids[i] >= 0 && ids[i] < v.size && v.cont[(size_t)ids[i]] ? 1 : 0;
+    return 0;
+}
 
 // Token ids of n texts (UTF-8, NFC), concatenated; off[h]..off[h+1] per text.  Returns the
 // total id count; if it exceeds cap nothing past cap is written and the caller retries with

@@ -34,6 +34,7 @@ class NBest:
     utt_ids: List[str]
     hyp_ids: List[str]
     lens: Optional[np.ndarray] = None   # per-hypothesis len(text) when built from text
+    word_start: Optional[np.ndarray] = None   # uint8 [sum T]: 1 where a word begins (``pll_spans``)
 
     @property
     def n_hyp(self) -> int:
@@ -64,14 +65,18 @@ class NBest:
                      (np.asarray(self.hyp_off[h0:h1 + 1], np.int64) - t0).astype(np.int32),
                      (np.asarray(self.utt_off[u0:u1 + 1], np.int64) - h0).astype(np.int32),
                      np.asarray(self.am[h0:h1], np.float64), list(self.refs[u0:u1]),
-                     list(self.utt_ids[u0:u1]), list(self.hyp_ids[h0:h1]))
+                     list(self.utt_ids[u0:u1]), list(self.hyp_ids[h0:h1]),
+                     word_start=None if self.word_start is None
+                     else np.ascontiguousarray(self.word_start[t0:t1], np.uint8))
 
     def subset(self, utts: Sequence[int]) -> "NBest":
-        toks, hoff, uoff, am, hyp_ids, refs, uids = [], [0], [0], [], [], [], []
+        toks, hoff, uoff, am, hyp_ids, refs, uids, ws = [], [0], [0], [], [], [], [], []
         for u in utts:
             for h in range(self.utt_off[u], self.utt_off[u + 1]):
                 seg = self.tokens[self.hyp_off[h]:self.hyp_off[h + 1]]
                 toks.append(seg)
+                if self.word_start is not None:
+                    ws.append(self.word_start[self.hyp_off[h]:self.hyp_off[h + 1]])
                 hoff.append(hoff[-1] + len(seg))
                 am.append(self.am[h])
                 hyp_ids.append(self.hyp_ids[h])
@@ -80,7 +85,56 @@ class NBest:
             uids.append(self.utt_ids[u])
         return NBest(np.concatenate(toks).astype(np.int32) if toks else np.zeros(0, np.int32),
                      np.asarray(hoff, np.int32), np.asarray(uoff, np.int32),
-                     np.asarray(am, np.float64), refs, uids, hyp_ids)
+                     np.asarray(am, np.float64), refs, uids, hyp_ids,
+                     word_start=None if self.word_start is None
+                     else (np.concatenate(ws).astype(np.uint8) if ws else np.zeros(0, np.uint8)))
+
+
+PLL_VARIANTS = ("original", "word_l2r", "whole_word")
+
+
+def pll_spans(hyp_off, word_start, variant: str = "original"):
+    """Rows of ``rs_pll_score_spans`` for a PLL variant: per hypothesis L = T - 2 rows, row p
+    (p = 1..L, in order) scored at ``query = p`` with positions ``[lo, hi)`` masked.
+
+    * ``"original"``   — ``[p, p + 1)``: Salazar et al.'s PLL, the rows of ``rs_pll_score``;
+    * ``"word_l2r"``   — ``[p, end of p's word)``: the target and the within-word pieces to its
+      right (Kauf & Ivanova 2023, PLL-word-l2r);
+    * ``"whole_word"`` — ``[begin of p's word, end of p's word)`` (PLL-whole-word).
+
+    ``word_start``: uint8 per token, 1 where a word begins ([CLS] and [SEP] are 1; the first
+    word piece of a hypothesis begins a word whatever its flag says).  ``None`` is allowed for
+    ``"original"`` only.  Returns int32 arrays ``(row_off [H + 1], lo, hi, query)``, positions
+    relative to the hypothesis."""
+    if variant not in PLL_VARIANTS:
+        raise ValueError(f"unknown PLL variant {variant!r} {PLL_VARIANTS}")
+    off = np.asarray(hyp_off, np.int64)
+    if len(off) < 1 or (np.diff(off) < 2).any():
+        raise ValueError("every hypothesis needs [CLS] and [SEP]")
+    L = np.diff(off) - 2
+    row_off = np.zeros(len(off), np.int64)
+    row_off[1:] = np.cumsum(L)
+    R = int(row_off[-1])
+    # row r -> its position p in its hypothesis and the token index of that position
+    hyp = np.repeat(np.arange(len(L)), L)
+    p = np.arange(R) - row_off[hyp] + 1
+    if variant == "original":
+        lo, hi = p, p + 1
+    else:
+        if word_start is None:
+            raise ValueError(f"variant {variant!r} needs word_start")
+        ws = np.asarray(word_start).astype(bool).copy()
+        if len(ws) != int(off[-1]):
+            raise ValueError("word_start must have one entry per token")
+        ws[off[:-1]] = True            # [CLS]
+        ws[off[:-1] + 1] = True        # the first word piece (or [SEP] when L = 0) begins a word
+        ws[off[1:] - 1] = True         # [SEP] ends the last word
+        starts = np.flatnonzero(ws)
+        g = off[hyp] + p               # global token index of the row's position
+        k = np.searchsorted(starts, g, side="right")     # starts[k - 1] <= g < starts[k]
+        hi = starts[k] - off[hyp]
+        lo = p if variant == "word_l2r" else starts[k - 1] - off[hyp]
+    return (row_off.astype(np.int32), np.asarray(lo, np.int32), np.asarray(hi, np.int32), p.astype(np.int32))
 
 
 def from_lists(hyps: List[List[Sequence[int]]], am: Optional[List[List[float]]] = None,

@@ -69,9 +69,20 @@ class NativeTokenizer:
     def encode_words(self, text: str) -> List[int]:
         return self.encode(text, add_special=False)
 
+    def word_starts(self, ids) -> np.ndarray:
+        """uint8 per id: 1 where the token begins a word, i.e. its vocabulary entry is no ``##``
+        continuation piece ([CLS], [SEP], [UNK] and ids outside the vocabulary begin a word): the
+        ``word_start`` of ``data.pll_spans``."""
+        a = np.ascontiguousarray(ids, np.int32)
+        cont = np.zeros(len(a), np.uint8)
+        if self.lib.rs_vocab_continuation(self.handle, a.ctypes.data, len(a), cont.ctypes.data) != 0:
+            raise ValueError("rs_vocab_continuation: bad arguments")
+        return (1 - cont).astype(np.uint8)
+
     def encode_nbest(self, hyps_text: Dict[str, Dict[str, str]], n_best: int = 1 << 30,
-                     max_utt: int = 1 << 30):
-        """N-best texts -> (tokens, hyp_off, utt_off, keys) in JSON key order."""
+                     max_utt: int = 1 << 30, return_word_start: bool = False):
+        """N-best texts -> (tokens, hyp_off, utt_off, keys) in JSON key order; with
+        ``return_word_start`` a fifth item, ``word_starts(tokens)``."""
         texts, keys, uoff = [], [], [0]
         for u, (uid, hyps) in enumerate(hyps_text.items()):
             if u == max_utt:
@@ -83,7 +94,8 @@ class NativeTokenizer:
                 keys.append((uid, hid))
             uoff.append(len(texts))
         ids, off = self.encode_batch(texts, add_special=True)
-        return ids, off.astype(np.int32), np.asarray(uoff, np.int32), keys
+        out = (ids, off.astype(np.int32), np.asarray(uoff, np.int32), keys)
+        return out + (self.word_starts(ids),) if return_word_start else out
 
 
 def json_saving(path: str, data: Dict[str, Dict[str, float]]) -> None:

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .data import NBest
+from .data import NBest, PLL_VARIANTS, pll_spans
 from .weights import BertShape, BERT_BASE
 
 
@@ -121,10 +121,19 @@ class PLLScorer(BertEngine):
         # BertForMaskedLM; "fp16" is an opt-in reduced-precision fast mode
         super().__init__(weights, shape, _lib.RS_HEAD_MLM, device, max_rows, precision)
 
-    def score_nbest(self, tokens, hyp_off, return_rows: bool = False):
+    def score_nbest(self, tokens, hyp_off, return_rows: bool = False, variant: str = "original", word_start=None):
         """tokens int32 [sum T] ([CLS] w.. [SEP] per hypothesis), hyp_off int [H+1].
 
+        ``variant``: "original" (``rs_pll_score``), or "word_l2r" / "whole_word" (``data.pll_spans``
+        over ``word_start``, uint8 per token, through ``score_spans``).
+
         Returns float64 [H] device tensor of PLL (and float32 per-row log-probs)."""
+        if variant != "original":
+            if variant not in PLL_VARIANTS:
+                raise ValueError(f"unknown PLL variant {variant!r} {PLL_VARIANTS}")
+            if word_start is None:
+                raise ValueError(f"variant {variant!r} needs word_start")
+            return self.score_spans(tokens, hyp_off, *pll_spans(hyp_off, word_start, variant), return_rows=return_rows)
         off = np.ascontiguousarray(hyp_off, np.int32)
         n_hyp = len(off) - 1
         d_tok = self._dev_tokens(tokens)
@@ -133,6 +142,31 @@ class PLLScorer(BertEngine):
         rows = torch.empty(n_rows, dtype=torch.float32, device=self.device) if return_rows else None
         _lib.check(self.lib.rs_pll_score(self.handle, _lib.ptr(d_tok), off.ctypes.data, n_hyp,
                                          _lib.ptr(pll), _lib.ptr(rows), _lib.stream_ptr(self.device)))
+        return (pll, rows) if return_rows else pll
+
+    def score_spans(self, tokens, hyp_off, row_off, lo, hi, query, return_rows: bool = False):
+        """Span-masked PLL (``rs_pll_score_spans``): row r of hypothesis h (``row_off[h] <= r <
+        row_off[h + 1]``) is the hypothesis with positions ``[lo[r], hi[r])`` replaced by [MASK],
+        scored at ``query[r]`` (positions relative to the hypothesis, ``1 <= lo <= query < hi <=
+        T - 1``).  Rows may come in any order, repeat and skip positions.
+
+        Returns float64 [H] device tensor (sum of each hypothesis' rows in row order; no rows: 0)
+        and, with ``return_rows``, the float32 per-row log-probs."""
+        off = np.ascontiguousarray(hyp_off, np.int32)
+        n_hyp = len(off) - 1
+        roff = np.ascontiguousarray(row_off, np.int32)
+        if len(roff) != n_hyp + 1:
+            raise ValueError("row_off must have one entry per hypothesis plus one")
+        n_rows = max(int(roff[-1]), 0) if n_hyp else 0
+        cols = [None if c is None else np.ascontiguousarray(c, np.int32) for c in (lo, hi, query)]
+        if any(c is not None and len(c) != n_rows for c in cols):
+            raise ValueError("lo, hi and query must have row_off[-1] entries")
+        d_tok = self._dev_tokens(tokens)
+        pll = torch.empty(n_hyp, dtype=torch.float64, device=self.device)
+        rows = torch.empty(n_rows, dtype=torch.float32, device=self.device) if return_rows else None
+        _lib.check(self.lib.rs_pll_score_spans(self.handle, _lib.ptr(d_tok), off.ctypes.data, n_hyp, roff.ctypes.data,
+                                               *[_lib.ptr(c) for c in cols], _lib.ptr(pll), _lib.ptr(rows),
+                                               _lib.stream_ptr(self.device)))
         return (pll, rows) if return_rows else pll
 
     def score(self, nb: NBest) -> np.ndarray:

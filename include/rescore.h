@@ -113,7 +113,7 @@ int rs_model_finalize(rs_model* m);
  * (>= 512).  Optional: scoring calls reserve a default on first use. */
 int rs_model_reserve(rs_model* m, int64_t max_rows);
 
-/* Range guard of the scoring calls (rs_pll_score, rs_masked_logprob, rs_masked_topk, rs_pll_topk,
+/* Range guard of the scoring calls (rs_pll_score, rs_pll_score_spans, rs_masked_logprob, rs_masked_topk, rs_pll_topk,
  * rs_cls_score, rs_token_embed, rs_bertscore_recall): after the last launch the call checks its outputs
  * for non-finite values (an operand image that overflowed fp16 turns every dependent score
  * into inf / NaN), synchronises `stream` and returns RS_EUNSUP with a message instead of
@@ -141,6 +141,29 @@ int rs_check(rs_model* m, void* stream);
  * The L masked copies are expanded on device. */
 int rs_pll_score(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off, int32_t n_hyp,
                  double* d_pll, float* d_row_lp, void* stream);
+
+/* Span-masked PLL: rs_pll_score with a caller-given list of scored rows per hypothesis, each row
+ * masking a range of positions instead of one.  Reference seam: MLM_PLL/preprocess.py:9-30
+ * generalised (do_job masks exactly position p in row p); the word variants are Kauf & Ivanova
+ * 2023, "A Better Way to Do Masked Language Model Scoring" (no reference counterpart).
+ *   h_row_off  int32 [n_hyp + 1] host   rows of hypothesis h: [h_row_off[h], h_row_off[h+1]);
+ *                                       ascending, h_row_off[0] == 0
+ *   h_lo, h_hi, h_query  int32 [h_row_off[n_hyp]] host, positions relative to the hypothesis:
+ *                        row r is the hypothesis with positions [lo_r, hi_r) replaced by [MASK],
+ *                        scored at query_r; 1 <= lo <= query < hi <= T - 1 ([CLS] and [SEP] are
+ *                        never masked), anything else RS_EARG with a message naming the row
+ *   d_row_lp   float32 [h_row_off[n_hyp]] or NULL: log_softmax(logits[query_r])[tok[query_r]]
+ *   d_pll      float64 [n_hyp]: the sum of the hypothesis' rows in row order; no rows: 0.0
+ * Rows of a hypothesis may come in any order, repeat and skip positions (a scored sub-range, a
+ * strided approximation).  Rows (p, p + 1, p) for p = 1..L are rs_pll_score's, bit for bit.
+ *   PLL-word-l2r:    row p masks [p, end of p's word)
+ *   PLL-whole-word:  row p masks [begin of p's word, end of p's word)
+ * Precision modes, chunking, layer-0 dedup (a run of copies shares one [MASK] row per masked
+ * position), the last-layer query path, the range guard and deferred checks are those of
+ * rs_pll_score; a model without the MLM head: RS_ESTATE. */
+int rs_pll_score_spans(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off, int32_t n_hyp,
+                       const int32_t* h_row_off, const int32_t* h_lo, const int32_t* h_hi,
+                       const int32_t* h_query, double* d_pll, float* d_row_lp, void* stream);
 
 /* Row-level MLM drop-in (MLM_PLL/main.py:89-105 for an arbitrary batch):
  *   d_ids      int32 ragged sequences (already masked), h_seq_off int32 [n_seq+1] host
@@ -392,6 +415,13 @@ int rs_ref_edit(const int32_t* d_chars, const int32_t* d_str_off, const int32_t*
 void* rs_vocab_load(const char* path);
 int rs_vocab_size(const void* vocab);
 void rs_vocab_free(void* vocab);
+
+/* out[i] = 1 where the vocabulary entry of ids[i] starts with "##" (a WordPiece continuation piece:
+ * the token continues the word of the token before it), else 0; ids outside [0, size) give 0.
+ * ids int32 [n], out uint8 [n].  A word of the tokenised text begins at every token whose flag is
+ * 0 ([CLS], [SEP] and [UNK] included): the word boundaries rs_pll_score_spans' word variants mask
+ * by.  Returns 0, or -1 on bad arguments. */
+int rs_vocab_continuation(const void* vocab, const int32_t* ids, int64_t n, uint8_t* out);
 
 /* BertTokenizer(vocab, do_lower_case=True).tokenize + convert_tokens_to_ids for n NFC UTF-8
  * texts, optionally wrapped in [CLS] .. [SEP] (add_special != 0): the ragged token layout
