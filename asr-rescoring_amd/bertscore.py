@@ -73,14 +73,16 @@ class BertScorer(BertEngine):
         super().__init__(truncate_weights(weights, num_layers), sh, _lib.RS_HEAD_EMB, device, max_rows,
                          precision)
 
-    def embed(self, tokens, hyp_off) -> torch.Tensor:
+    def embed(self, tokens, hyp_off, token_types=None) -> torch.Tensor:
         """[sum T, H]: L2-normalised last hidden state of every token — float32 (hi + lo/64 of
-        the two-part image) in the fp16x3 mode, fp16 in the fp16 mode."""
+        the two-part image) in the fp16x3 mode, fp16 in the fp16 mode.  ``token_types``: one
+        segment id per token."""
         off = np.ascontiguousarray(hyp_off, np.int32)
         d_tok = self._dev_tokens(tokens)
         H, two = self.shape.hidden, self.precision == "fp16x3"
         out = torch.empty(int(off[-1]) if len(off) else 0, H * (2 if two else 1), dtype=torch.float16,
                           device=self.device)
+        d_type = self._set_types(token_types)      # noqa: F841
         _lib.check(self.lib.rs_token_embed(self.handle, _lib.ptr(d_tok), off.ctypes.data, len(off) - 1,
                                            _lib.ptr(out), _lib.stream_ptr(self.device)))
         if two:

@@ -15,7 +15,10 @@ generator when ``random_init_seed`` is set.  The tokenizer is ``BertTokenizer``-
 per-character for CJK (``data.CharTokenizer``) built from the data, unless ``model.vocab``
 names a ``vocab.txt`` — then the native BertTokenizer-compatible ``frontend.NativeTokenizer``
 (and score JSON is written by the native ``frontend.json_saving``).  Extra keys: ``precision`` (fp16 / fp16x3), ``max_rows``,
-``mode`` (rescore fusion formula: norm / legacy / am_norm), ``pll_variant`` (mlm_pll: original / word_l2r / whole_word).
+``mode`` (rescore fusion formula: norm / legacy / am_norm), ``pll_variant`` (mlm_pll: original / word_l2r / whole_word),
+``{split}_context_text_path`` (mlm_pll, mlm_topk, rescorebert, rescorebert_train: JSON ``{utt_id: text}``; every
+hypothesis of the utterance becomes the pair ``[CLS] context [SEP] hypothesis [SEP]`` with segment ids 0 / 1,
+``data.with_context``; a missing utterance has no context; MLM scores cover the hypothesis half only).
 """
 from __future__ import annotations
 
@@ -77,6 +80,32 @@ def _nbest_tokens(hyps_text: Dict[str, Dict[str, str]], tok, max_utt=1 << 30, n_
     return D.from_lists(words), keys
 
 
+def _context_texts(cfg, split: str):
+    """``{split}_context_text_path``: ``{utt_id: text}`` or None without the key."""
+    path = get(cfg, f"{split}_context_text_path")
+    return _load(path) if path else None
+
+
+def _with_context(ctx, uids, tok, tokens, hyp_off, utt_off, word_start=None):
+    """``data.with_context`` over the utterances ``uids`` (one per ``utt_off`` group) with the texts
+    of ``ctx`` tokenised by ``tok``; pairs are cut to BERT's 512 positions from the context's left."""
+    seqs = [list(tok.encode_words(ctx[u])) if u in ctx else [] for u in uids]
+    c_tok = np.asarray([x for sq in seqs for x in sq], np.int32)
+    c_off = np.concatenate([[0], np.cumsum([len(sq) for sq in seqs])]).astype(np.int32)
+    c_ws = tok.word_starts(c_tok) if word_start is not None and hasattr(tok, "word_starts") else None
+    return D.with_context(tokens, hyp_off, utt_off, c_tok, c_off, BERT_BASE.max_pos, word_start, c_ws)
+
+
+def _nbest_context(hyps_text, tok, nb, ctx):
+    """The ``NBest`` of ``_nbest_tokens`` as context pairs (``token_type`` / ``score_from`` set)."""
+    if ctx is None:
+        return nb
+    tokens, off, tt, sf, ws = _with_context(ctx, list(hyps_text)[:nb.n_utt], tok, nb.tokens, nb.hyp_off, nb.utt_off,
+                                            nb.word_start)
+    nb.tokens, nb.hyp_off, nb.token_type, nb.score_from, nb.word_start = tokens, off, tt, sf, ws
+    return nb
+
+
 def _pll_variant(cfg) -> str:
     v = str(get(cfg, "pll_variant", "original"))
     if v not in D.PLL_VARIANTS:
@@ -90,6 +119,8 @@ def mlm_pll(cfg) -> Dict[str, str]:
     rows (``*_data_path``: do_job output) or raw ``*_hyps_text_path`` JSON.  Extra key
     ``pll_variant`` (text inputs only): ``original`` (default), ``word_l2r`` or ``whole_word`` (Kauf &
     Ivanova 2023; ``data.pll_spans`` over the word boundaries of the native tokenizer's WordPiece output).
+    Extra key ``{split}_context_text_path`` (text inputs only): the hypotheses are scored as the second
+    segment of ``[CLS] context [SEP] hypothesis [SEP]``, at the hypothesis' positions only.
 
     Launched with torchrun (WORLD_SIZE > 1): one process per GPU, each scores a contiguous,
     cost-balanced utterance range (``shard.plan_shards``); the scores meet in one all-gather
@@ -103,6 +134,11 @@ def mlm_pll(cfg) -> Dict[str, str]:
             if rows_path and os.path.exists(rows_path):
                 raise ValueError(f"pll_variant {variant!r} needs {split}_hyps_text_path: the rows of "
                                  f"{split}_data_path are already masked one position each")
+    for split in ("train", "dev", "test"):
+        rows_path = get(cfg, f"{split}_data_path")
+        if get(cfg, f"{split}_context_text_path") and rows_path and os.path.exists(rows_path):
+            raise ValueError(f"{split}_context_text_path needs {split}_hyps_text_path: the rows of "
+                             f"{split}_data_path are single segments already")
     rank, world, local = shard.init_from_env()
     device = local if world > 1 else _dev(cfg)
     scorer = PLLScorer(_weights(cfg, "mlm"), BERT_BASE, device=device, max_rows=get(cfg, "max_rows", 65536),
@@ -116,7 +152,8 @@ def mlm_pll(cfg) -> Dict[str, str]:
             output_score = _score_rows_sharded(scorer, rows, rank, world)
         elif text_path and os.path.exists(text_path):
             hyps = _load(text_path)
-            tok = _tokenizer(cfg, [t for h in hyps.values() for t in h.values()])
+            ctx = _context_texts(cfg, split)
+            tok = _tokenizer(cfg, [t for h in hyps.values() for t in h.values()] + list((ctx or {}).values()))
             nb, keys = _nbest_tokens(hyps, tok)
             use = variant
             if variant != "original" and not hasattr(tok, "word_starts"):
@@ -127,8 +164,11 @@ def mlm_pll(cfg) -> Dict[str, str]:
                 use = "original"
             if use != "original":
                 nb.word_start = tok.word_starts(nb.tokens)
+            nb = _nbest_context(hyps, tok, nb, ctx)
             both = shard.score_sharded(nb, lambda sub: scorer.score_nbest(sub.tokens, sub.hyp_off, variant=use,
-                                                                          word_start=sub.word_start))
+                                                                          word_start=sub.word_start,
+                                                                          token_types=sub.token_type,
+                                                                          score_from=sub.score_from))
             pll = both[1].cpu().numpy()
             output_score = {}
             for (u, h), s in zip(keys, pll):
@@ -152,7 +192,8 @@ def mlm_topk(cfg) -> Dict[str, str]:
     MLM_PLL/main.py:101-105 before the label gather, through ``PLLScorer.topk_nbest``.  No reference
     counterpart.  For each split with ``{split}_hyps_text_path`` writes ``{split}_topk.json``:
     ``{utt: {hyp: {"ids": [[k ids] per position], "logprob": [[k floats] per position]}}}``.
-    Weight, tokenizer, precision, device and ``max_rows`` keys as ``mlm_pll``; single-process."""
+    Weight, tokenizer, precision, device and ``max_rows`` keys as ``mlm_pll``; single-process.
+    With ``{split}_context_text_path`` the rows are those of the hypothesis half of the pair."""
     from .scorer import PLLScorer
     scorer = PLLScorer(_weights(cfg, "mlm"), BERT_BASE, device=_dev(cfg), max_rows=get(cfg, "max_rows", 65536),
                        precision=get(cfg, "precision", "fp16x3"))
@@ -163,14 +204,17 @@ def mlm_topk(cfg) -> Dict[str, str]:
         if not (text_path and os.path.exists(text_path)):
             continue
         hyps = _load(text_path)
-        tok = _tokenizer(cfg, [t for h in hyps.values() for t in h.values()])
+        ctx = _context_texts(cfg, split)
+        tok = _tokenizer(cfg, [t for h in hyps.values() for t in h.values()] + list((ctx or {}).values()))
         nb, keys = _nbest_tokens(hyps, tok, int(get(cfg, "max_utt", 1 << 30)), int(get(cfg, "n_best", 1)))
-        ids, lp = scorer.topk_nbest(nb.tokens, nb.hyp_off, k)
+        nb = _nbest_context(hyps, tok, nb, ctx)
+        ids, lp = scorer.topk_nbest(nb.tokens, nb.hyp_off, k, token_types=nb.token_type)
         ids, lp = ids.cpu().tolist(), lp.cpu().tolist()
         row_off = np.concatenate([[0], np.cumsum(np.diff(nb.hyp_off) - 2)])
+        skip = np.zeros(nb.n_hyp, np.int64) if nb.score_from is None else nb.score_from.astype(np.int64) - 1
         out = {}
         for h, (u, hid) in enumerate(keys):
-            a, b = int(row_off[h]), int(row_off[h + 1])
+            a, b = int(row_off[h] + skip[h]), int(row_off[h + 1])       # the hypothesis' own positions
             out.setdefault(u, {})[hid] = {"ids": ids[a:b], "logprob": lp[a:b]}
         path = cfg.output_path + f"{split}_topk.json"
         with open(path, "w", encoding="utf-8") as f:
@@ -292,7 +336,8 @@ def mlm_finetune(cfg) -> Dict[str, object]:
 
 
 def rescorebert(cfg) -> Dict[str, str]:
-    """RescoreBert/main.py:232-285 (score): dev/test hyps -> CLS scores -> dev_lm/test_lm.json."""
+    """RescoreBert/main.py:232-285 (score): dev/test hyps -> CLS scores -> dev_lm/test_lm.json.
+    With ``{split}_context_text_path`` every hypothesis is scored as a context pair."""
     from .scorer import RescoreBertScorer
     sc = RescoreBertScorer(_weights(cfg, "cls"), BERT_BASE, device=_dev(cfg), max_rows=get(cfg, "max_rows", 65536),
                            precision=get(cfg, "precision", "fp16x3"))
@@ -304,9 +349,11 @@ def rescorebert(cfg) -> Dict[str, str]:
         if "hyps_token_ids" not in feats or not fmt or not os.path.exists(fmt):
             continue
         hyps = _load(paths[feats.index("hyps_token_ids")])
-        tok = _tokenizer(cfg, [t for h in hyps.values() for t in h.values()])
+        ctx = _context_texts(cfg, split)
+        tok = _tokenizer(cfg, [t for h in hyps.values() for t in h.values()] + list((ctx or {}).values()))
         max_utt, n_best = get(cfg, "max_utt", 1 << 30), get(cfg, "n_best", 1 << 30)
         nb, keys = _nbest_tokens(hyps, tok, max_utt, n_best)
+        nb = _nbest_context(hyps, tok, nb, ctx)
         scores = sc.score(nb)
         out = D.get_output_format(fmt, max_utt, n_best)      # util/get_output_format.py:4-16
         for (u, h), s in zip(keys, scores):
@@ -339,10 +386,15 @@ def _rb_features(cfg, split: str):
     out = {"keys": keys, "features": list(feats)}
     if "hyps_token_ids" in src:
         texts = src["hyps_token_ids"]
-        tok = _tokenizer(cfg, [t for h in texts.values() for t in h.values()])
+        ctx = _context_texts(cfg, split)
+        tok = _tokenizer(cfg, [t for h in texts.values() for t in h.values()] + list((ctx or {}).values()))
         seqs = [[D.CLS_ID] + list(tok.encode_words(texts[u][h])) + [D.SEP_ID] for u, h in keys]
         out["tokens"] = np.asarray([x for sq in seqs for x in sq], np.int32)
         out["hyp_off"] = np.concatenate([[0], np.cumsum([len(sq) for sq in seqs])]).astype(np.int32)
+        if ctx is not None:       # context pairs: runs of one utterance's rows share its context
+            first = [i for i, (u, _) in enumerate(keys) if i == 0 or u != keys[i - 1][0]]
+            out["tokens"], out["hyp_off"], out["token_type"], _, _ = _with_context(
+                ctx, [keys[i][0] for i in first], tok, out["tokens"], out["hyp_off"], first + [len(keys)])
     for f in ("mlm_pll_score", "hyps_am_score", "hyps_cer"):
         if f in src:
             out[f] = np.asarray([src[f][u][h] for u, h in keys], np.float32)
@@ -356,7 +408,8 @@ def rescorebert_train(cfg) -> Dict[str, object]:
     ``md_loss_weight``, ``lr``, ``epoch``, ``batch_size`` (utterances: batch_size * n_best
     rows), ``n_best``, ``max_utt``, ``train_feature`` / ``train_feature_path`` and ``dev_*``
     (hyps_token_ids = the hypothesis text JSON, mlm_pll_score, hyps_am_score, hyps_cer),
-    ``output_path``, ``resume.start_from`` / ``resume.checkpoint_path``.  Per epoch: a fresh
+    ``output_path``, ``resume.start_from`` / ``resume.checkpoint_path``, ``train_context_text_path`` /
+    ``dev_context_text_path`` (context pairs with segment ids).  Per epoch: a fresh
     AdamW (``:83-86``), the train pass, the dev loss (no update), ``checkpoint_{epoch}.pth``
     and ``loss.json``.  Extra: ``checkpoint_path`` / ``random_init_seed`` (initial weights:
     bert-base-chinese cannot be fetched offline), ``weight_decay``, dropout keys (``_dropout_args``)."""
@@ -385,7 +438,7 @@ def rescorebert_train(cfg) -> Dict[str, object]:
     def epoch_pass(f, update):
         z = np.zeros(len(f["hyp_off"]) - 1, np.float32)
         return rescorebert_epoch(tr, f["tokens"], f["hyp_off"], f["mlm_pll_score"], f.get("hyps_am_score", z),
-                                 f.get("hyps_cer", z), bs, n_best, update=update)
+                                 f.get("hyps_cer", z), bs, n_best, update=update, token_types=f.get("token_type"))
     ckpts = []
     try:
         for ep in range(int(start) if resume else 1, int(get(cfg, "epoch", 1)) + 1):

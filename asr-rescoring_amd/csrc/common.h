@@ -190,8 +190,9 @@ __device__ __forceinline__ float ln_apply(float x, float2 st, float g, float b) 
 
 // embed_ln writes the pre-LN embedding sum (x32), its row statistics and the fp16 operand
 // image of LN(x); ln_rows writes the operand image, the statistics and (y32 != null) LN(x).
-hipError_t launch_embed_ln(const int* tok, SeqMeta sm, int s0, int s1, int row0, int mask_id,
-                           int vocab, const float* word, const float* pos, const float* type0,
+// type (nullable): segment ids parallel to tok (clamped to [0, type_vocab)); typetab [type_vocab, H].
+hipError_t launch_embed_ln(const int* tok, const int* type, SeqMeta sm, int s0, int s1, int row0, int mask_id,
+                           int vocab, int type_vocab, const float* word, const float* pos, const float* typetab,
                            const float* g, const float* b, float eps, int H, float* x32,
                            float2* stats, f16* h16, int kx, hipStream_t st);
 hipError_t launch_ln_rows(const float* x, int rows, const float* g, const float* b, float eps,
@@ -216,9 +217,9 @@ hipError_t launch_ln_res_img(f16* h16, const float* o32, int rows, const float* 
 // Unique layer-0 rows (dedup): the urows rows of the chunk's plan (seq_plan.h: per run of copies of
 // a hypothesis its T rows, then the [MASK] rows of the run's masked range), as the fp16 operand
 // image of LN(embedding) (rows of SeqMeta.urow_*)
-hipError_t launch_embed_unique(const int* tok, SeqMeta sm, int s0, int s1, int urows, int mask_id, int vocab,
-                               const float* word, const float* pos, const float* type0, const float* g,
-                               const float* b, float eps, int H, f16* h16u, int kx, hipStream_t st);
+hipError_t launch_embed_unique(const int* tok, const int* type, SeqMeta sm, int s0, int s1, int urows, int mask_id,
+                               int vocab, int type_vocab, const float* word, const float* pos, const float* typetab,
+                               const float* g, const float* b, float eps, int H, f16* h16u, int kx, hipStream_t st);
 // BERTScore recall matrix (k_bertscore.hip); items = (utterance, j0, j1, -) ref-column runs of
 // at most bertscore_cols(two) columns; two: emb is the two-part image (split-operand cosines)
 int bertscore_cols(bool two);

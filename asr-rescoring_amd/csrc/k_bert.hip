@@ -1,7 +1,7 @@
 // BERT encoder kernels other than the GEMMs and attention (k_attn.hip) (gfx950, wave64).
 //
 //  embed_ln        K1+K2: on-device [MASK] expansion (MLM_PLL/preprocess.py:15-21) fused with
-//                  BertEmbeddings (modeling_bert.py:53-108): word + type[0] + position -> LN
+//                  BertEmbeddings (modeling_bert.py:53-108): word + type[segment id, 0 without] + position -> LN
 //  ln_rows         LayerNorm of BertSelfOutput / BertOutput / head transform (eps 1e-12)
 //  lse_finalize    merges the decoder epilogue's (max, sum exp) slabs: log_softmax gather
 //                  (MLM_PLL/main.py:101-105)
@@ -56,13 +56,16 @@ __device__ __forceinline__ void ln_store(const float4 (&x)[NV], const float* g, 
 
 // Embedding sum of position t of a sequence (token t, or [MASK] when lo <= t < hi): the one
 // expression both the copy-row and the unique-row kernels use (bit-identical rows).
+// type (nullable): segment ids parallel to tok; a [MASK] row keeps the type of its position.
+// typetab: the whole [type_vocab, H] table; without segment ids every row adds its row 0.
 template <int NV>
-__device__ __forceinline__ void embed_row(const int* tok, int toff, int t, int lo, int hi, int mask_id, int vocab,
-                                          const float* word, const float* pos, const float* type0, int lane,
-                                          float4 (&x)[NV]) {
+__device__ __forceinline__ void embed_row(const int* tok, const int* type, int toff, int t, int lo, int hi,
+                                          int mask_id, int vocab, int type_vocab, const float* word, const float* pos,
+                                          const float* typetab, int lane, float4 (&x)[NV]) {
     constexpr int H = NV * 256;
     int id = (t >= lo && t < hi) ? mask_id : tok[toff + t];
     id = min(max(id, 0), vocab - 1);              // out-of-range ids are clamped, never read OOB
+    const float* type0 = typetab + (type ? (size_t)min(max(type[toff + t], 0), type_vocab - 1) * H : (size_t)0);
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
         const int c = v * 256 + lane * 4;
@@ -79,9 +82,9 @@ __device__ __forceinline__ void embed_row(const int* tok, int toff, int t, int l
 // unmasked rows, the last copy the run's [MASK] rows.  s1 - s0 blocks; urows: the chunk's count.
 template <int NV>
 __global__ void __launch_bounds__(256)
-embed_unique_kernel(const int* __restrict__ tok, SeqMeta sm, int s0, int urows, int mask_id, int vocab,
-                    const float* __restrict__ word, const float* __restrict__ pos,
-                    const float* __restrict__ type0, const float* __restrict__ g,
+embed_unique_kernel(const int* __restrict__ tok, const int* __restrict__ type, SeqMeta sm, int s0, int urows,
+                    int mask_id, int vocab, int type_vocab, const float* __restrict__ word,
+                    const float* __restrict__ pos, const float* __restrict__ typetab, const float* __restrict__ g,
                     const float* __restrict__ b, float eps, f16* __restrict__ h16u, int kx) {
     constexpr int H = NV * 256;
     const int s = s0 + blockIdx.x;
@@ -96,16 +99,17 @@ embed_unique_kernel(const int* __restrict__ tok, SeqMeta sm, int s0, int urows, 
         const int t = masked ? w.mask_pos + j : k;
         const size_t r = masked ? (size_t)(w.mask_row + j) : (size_t)(uh + k);
         float4 x[NV];
-        embed_row<NV>(tok, toff, t, masked ? t : -1, masked ? t + 1 : -1, mask_id, vocab, word, pos, type0, lane, x);
+        embed_row<NV>(tok, type, toff, t, masked ? t : -1, masked ? t + 1 : -1, mask_id, vocab, type_vocab, word, pos,
+                      typetab, lane, x);
         ln_store<NV>(x, g, b, eps, lane, nullptr, nullptr, h16u + r * kx * H, kx);
     }
 }
 
 template <int NV>
 __global__ void __launch_bounds__(256)
-embed_ln_kernel(const int* __restrict__ tok, SeqMeta sm, int s0, int row0, int mask_id, int vocab,
-                const float* __restrict__ word, const float* __restrict__ pos,
-                const float* __restrict__ type0, const float* __restrict__ g,
+embed_ln_kernel(const int* __restrict__ tok, const int* __restrict__ type, SeqMeta sm, int s0, int row0, int mask_id,
+                int vocab, int type_vocab, const float* __restrict__ word, const float* __restrict__ pos,
+                const float* __restrict__ typetab, const float* __restrict__ g,
                 const float* __restrict__ b, float eps, float* __restrict__ x32,
                 float2* __restrict__ stats, f16* __restrict__ h16, int kx) {
     constexpr int H = NV * 256;
@@ -115,7 +119,7 @@ embed_ln_kernel(const int* __restrict__ tok, SeqMeta sm, int s0, int row0, int m
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int t = wave; t < T; t += 4) {
         float4 x[NV];
-        embed_row<NV>(tok, toff, t, lo, hi, mask_id, vocab, word, pos, type0, lane, x);
+        embed_row<NV>(tok, type, toff, t, lo, hi, mask_id, vocab, type_vocab, word, pos, typetab, lane, x);
         const size_t r = (size_t)(rs + t);
 #pragma unroll
         for (int v = 0; v < NV; ++v) if (x32) *(float4*)(x32 + r * H + v * 256 + lane * 4) = x[v];
@@ -447,26 +451,26 @@ hipError_t launch_for_h(int H, Launch&& launch) {
 
 }  // namespace
 
-hipError_t launch_embed_ln(const int* tok, SeqMeta sm, int s0, int s1, int row0, int mask_id,
-                           int vocab, const float* word, const float* pos, const float* type0,
+hipError_t launch_embed_ln(const int* tok, const int* type, SeqMeta sm, int s0, int s1, int row0, int mask_id,
+                           int vocab, int type_vocab, const float* word, const float* pos, const float* typetab,
                            const float* g, const float* b, float eps, int H, float* x32,
                            float2* stats, f16* h16, int kx, hipStream_t st) {
     const int n = s1 - s0;
     if (n <= 0) return hipSuccess;
     return launch_for_h(H, [&](auto nv) {
-        hipLaunchKernelGGL(embed_ln_kernel<decltype(nv)::value>, dim3(n), dim3(256), 0, st, tok, sm, s0, row0, mask_id,
-                           vocab, word, pos, type0, g, b, eps, x32, stats, h16, kx);
+        hipLaunchKernelGGL(embed_ln_kernel<decltype(nv)::value>, dim3(n), dim3(256), 0, st, tok, type, sm, s0, row0,
+                           mask_id, vocab, type_vocab, word, pos, typetab, g, b, eps, x32, stats, h16, kx);
     });
 }
 
-hipError_t launch_embed_unique(const int* tok, SeqMeta sm, int s0, int s1, int urows, int mask_id, int vocab,
-                               const float* word, const float* pos, const float* type0, const float* g,
-                               const float* b, float eps, int H, f16* h16u, int kx, hipStream_t st) {
+hipError_t launch_embed_unique(const int* tok, const int* type, SeqMeta sm, int s0, int s1, int urows, int mask_id,
+                               int vocab, int type_vocab, const float* word, const float* pos, const float* typetab,
+                               const float* g, const float* b, float eps, int H, f16* h16u, int kx, hipStream_t st) {
     const int n = s1 - s0;
     if (n <= 0) return hipSuccess;
     return launch_for_h(H, [&](auto nv) {
-        hipLaunchKernelGGL(embed_unique_kernel<decltype(nv)::value>, dim3(n), dim3(256), 0, st, tok, sm, s0, urows,
-                           mask_id, vocab, word, pos, type0, g, b, eps, h16u, kx);
+        hipLaunchKernelGGL(embed_unique_kernel<decltype(nv)::value>, dim3(n), dim3(256), 0, st, tok, type, sm, s0, urows,
+                           mask_id, vocab, type_vocab, word, pos, typetab, g, b, eps, h16u, kx);
     });
 }
 

@@ -46,17 +46,19 @@ __device__ __forceinline__ void ln_fwd_row(const float4 (&x)[NV], const float* g
     }
 }
 
-// x0 = word[tok] + type[0] + pos[t]; h0 = LN(x0)
+// x0 = word[tok] + type[row_type, 0 without] + pos[t]; h0 = LN(x0)
 template <int NV>
 __global__ void __launch_bounds__(256)
-tr_embed_ln_kernel(const int* __restrict__ row_tok, const int* __restrict__ row_pos, int M, int vocab,
-                   const float* __restrict__ word, const float* __restrict__ pos, const float* __restrict__ type0,
+tr_embed_ln_kernel(const int* __restrict__ row_tok, const int* __restrict__ row_pos,
+                   const int* __restrict__ row_type, int M, int vocab, int type_vocab,
+                   const float* __restrict__ word, const float* __restrict__ pos, const float* __restrict__ typetab,
                    const float* __restrict__ g, const float* __restrict__ b, float eps, float* __restrict__ x0,
                    float2* __restrict__ st, float* __restrict__ h0, TrDrop dr) {
     constexpr int H = NV * 256;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= M) return;
     const int id = min(max(row_tok[row], 0), vocab - 1), t = row_pos[row];
+    const float* type0 = typetab + (row_type ? (size_t)min(max(row_type[row], 0), type_vocab - 1) * H : (size_t)0);
     float4 x[NV];
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
@@ -604,10 +606,12 @@ tr_ln_bwd_kernel(const float* dy, const float* __restrict__ x, const float2* __r
 // Column reductions, stage 1: partial[rb][c] over rows [64 rb, 64 rb + 64) in row order.
 //   mode 0: sum dy            (bias grads)
 //   mode 1: sum dy * xhat     (LN gamma; xhat from x and (mean, rstd))
+// rtype (nullable): row predicate, only rows with rtype[r] == want are summed (the rows are skipped,
+// so the order among the rest is the unpredicated one and a type without rows sums to exactly 0).
 constexpr int kRB = 64;
 __global__ void tr_colsum_partial_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                          const float2* __restrict__ st, int M, int N, int mode,
-                                         float* __restrict__ part) {
+                                         float* __restrict__ part, const int* __restrict__ rtype, int want) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x, rb = blockIdx.y;
     if (c >= N) return;
     const int r0 = rb * kRB, r1 = min(M, r0 + kRB);
@@ -616,10 +620,14 @@ __global__ void tr_colsum_partial_kernel(const float* __restrict__ dy, const flo
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     if (mode == 0) {
 #pragma unroll 8
-        for (int r = r0; r < r1; ++r) acc[r & 3] += dy[(size_t)r * N + c];
+        for (int r = r0; r < r1; ++r) {
+            if (rtype && rtype[r] != want) continue;
+            acc[r & 3] += dy[(size_t)r * N + c];
+        }
     } else {
 #pragma unroll 4
         for (int r = r0; r < r1; ++r) {
+            if (rtype && rtype[r] != want) continue;
             const float2 s = st[r];
             acc[r & 3] += dy[(size_t)r * N + c] * ((x[(size_t)r * N + c] - s.x) * s.y);
         }
@@ -639,7 +647,8 @@ constexpr int kRB4 = 128, kOnePass = 2048;
 template <int MODE, bool ONE>
 __global__ void __launch_bounds__(256)
 tr_colsum4_partial_kernel(const float* __restrict__ dy, const float* __restrict__ x, const float2* __restrict__ st,
-                          int M, int N, float* __restrict__ part0, float* __restrict__ part1, int accumulate) {
+                          int M, int N, float* __restrict__ part0, float* __restrict__ part1, int accumulate,
+                          const int* __restrict__ rtype, int want) {
     constexpr int CL = ONE ? 4 : 16, RL = 256 / CL, NQ = MODE == 2 ? 2 : 1;
     __shared__ float4 red[NQ][RL][CL];
     __shared__ float4 red8[NQ][RL / 8][CL];
@@ -650,6 +659,7 @@ tr_colsum4_partial_kernel(const float* __restrict__ dy, const float* __restrict_
     if (c < N) {
 #pragma unroll 4
         for (int r = r0 + rl; r < r1; r += RL) {
+            if (rtype && rtype[r] != want) continue;          // row predicate (tr_colsum_partial_kernel)
             const float4 d = *(const float4*)(dy + (size_t)r * N + c);
             if (MODE != 1) {
                 b.x += d.x; b.y += d.y; b.z += d.z; b.w += d.w;
@@ -961,12 +971,12 @@ int grid_for(long long n, int bs) { return (int)std::min<long long>((n + bs - 1)
         default: return hipErrorInvalidValue; \
     }
 
-hipError_t tr_embed_ln(const int* row_tok, const int* row_pos, int M, int vocab, const float* word,
-                       const float* pos, const float* type0, const float* g, const float* b, float eps, int H,
-                       float* x0, float2* st, float* h0, hipStream_t s, const TrDrop& d) {
+hipError_t tr_embed_ln(const int* row_tok, const int* row_pos, const int* row_type, int M, int vocab, int type_vocab,
+                       const float* word, const float* pos, const float* typetab, const float* g, const float* b,
+                       float eps, int H, float* x0, float2* st, float* h0, hipStream_t s, const TrDrop& d) {
     if (M <= 0) return hipSuccess;
     RS_NV_SWITCH(H, hipLaunchKernelGGL(tr_embed_ln_kernel<NV>, dim3((M + 3) / 4), dim3(256), 0, s, row_tok, row_pos,
-                                       M, vocab, word, pos, type0, g, b, eps, x0, st, h0, d));
+                                       row_type, M, vocab, type_vocab, word, pos, typetab, g, b, eps, x0, st, h0, d));
     return hipGetLastError();
 }
 
@@ -1118,27 +1128,27 @@ size_t tr_colsum_scratch(int M, int N) {
 }
 
 hipError_t tr_colsum(const float* dy, const float* x, const float2* st, int M, int N, int mode, float* part,
-                     float* out, int accumulate, hipStream_t s) {
+                     float* out, int accumulate, hipStream_t s, const int* rtype, int want) {
     if (M <= 0 || N <= 0) return hipSuccess;
     if (N % 4 == 0) {
         const dim3 g1((N + 63) / 64), g16((N + 15) / 16);
         if (M <= kOnePass) {
             if (mode == 0)
-                hipLaunchKernelGGL((tr_colsum4_partial_kernel<0, true>), g16, dim3(256), 0, s, dy, x, st, M, N, out, out, accumulate);
+                hipLaunchKernelGGL((tr_colsum4_partial_kernel<0, true>), g16, dim3(256), 0, s, dy, x, st, M, N, out, out, accumulate, rtype, want);
             else
-                hipLaunchKernelGGL((tr_colsum4_partial_kernel<1, true>), g16, dim3(256), 0, s, dy, x, st, M, N, out, out, accumulate);
+                hipLaunchKernelGGL((tr_colsum4_partial_kernel<1, true>), g16, dim3(256), 0, s, dy, x, st, M, N, out, out, accumulate, rtype, want);
             return hipGetLastError();
         }
         const int nrb = (M + kRB4 - 1) / kRB4;
         if (mode == 0)
-            hipLaunchKernelGGL((tr_colsum4_partial_kernel<0, false>), dim3(g1.x, nrb), dim3(256), 0, s, dy, x, st, M, N, part, part, 0);
+            hipLaunchKernelGGL((tr_colsum4_partial_kernel<0, false>), dim3(g1.x, nrb), dim3(256), 0, s, dy, x, st, M, N, part, part, 0, rtype, want);
         else
-            hipLaunchKernelGGL((tr_colsum4_partial_kernel<1, false>), dim3(g1.x, nrb), dim3(256), 0, s, dy, x, st, M, N, part, part, 0);
+            hipLaunchKernelGGL((tr_colsum4_partial_kernel<1, false>), dim3(g1.x, nrb), dim3(256), 0, s, dy, x, st, M, N, part, part, 0, rtype, want);
         hipLaunchKernelGGL(tr_colsum_final_kernel, g1, dim3(64), 0, s, part, nrb, N, out, accumulate);
         return hipGetLastError();
     }
     const int nrb = (M + kRB - 1) / kRB;
-    hipLaunchKernelGGL(tr_colsum_partial_kernel, dim3((N + 255) / 256, nrb), dim3(256), 0, s, dy, x, st, M, N, mode, part);
+    hipLaunchKernelGGL(tr_colsum_partial_kernel, dim3((N + 255) / 256, nrb), dim3(256), 0, s, dy, x, st, M, N, mode, part, rtype, want);
     hipLaunchKernelGGL(tr_colsum_final_kernel, dim3((N + 63) / 64), dim3(64), 0, s, part, nrb, N, out, accumulate);
     return hipGetLastError();
 }
@@ -1154,13 +1164,13 @@ hipError_t tr_colsum_ln(const float* dy, const float* x, const float2* st, int M
     }
     if (M <= kOnePass) {
         hipLaunchKernelGGL((tr_colsum4_partial_kernel<2, true>), dim3((N + 15) / 16), dim3(256), 0, s, dy, x, st, M, N, out_g,
-                           out_b, 0);
+                           out_b, 0, nullptr, 0);
         return hipGetLastError();
     }
     const int nrb = (M + kRB4 - 1) / kRB4;
     float* part_b = part + (size_t)nrb * N;         // tr_colsum_scratch: room for two
     hipLaunchKernelGGL((tr_colsum4_partial_kernel<2, false>), dim3((N + 63) / 64, nrb), dim3(256), 0, s, dy, x, st, M, N, part,
-                       part_b, 0);
+                       part_b, 0, nullptr, 0);
     hipLaunchKernelGGL(tr_colsum_final_kernel, dim3((N + 63) / 64), dim3(64), 0, s, part, nrb, N, out_g, 0);
     hipLaunchKernelGGL(tr_colsum_final_kernel, dim3((N + 63) / 64), dim3(64), 0, s, part_b, nrb, N, out_b, 0);
     return hipGetLastError();

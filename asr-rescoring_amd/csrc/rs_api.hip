@@ -123,6 +123,11 @@ struct rs_model {
     int32_t* topk_id = nullptr;
     float* topk_lp = nullptr;
     DevBuf topk_cand;           // topk_cand_bytes(vpad)
+    // rs_model_set_token_types (TypeCall): segment ids of the next encoder call, [type_n] device ints
+    // parallel to its tokens; type_cur: the ids of the call that is running (null: every row type 0)
+    const int32_t* type_next = nullptr;
+    int64_t type_n = 0;
+    const int32_t* type_cur = nullptr;
     DevBuf emb, plan;           // rs_bertscore_recall: token embeddings, work-item plan
     DevBuf flag;                // non-finite-output flag of the last scoring call(s) (range guard)
     bool sync_check = true;     // scoring calls synchronise and report their flags (rs_model_set_sync_check)
@@ -559,12 +564,15 @@ struct ChunkCtx {
         // GEMM operand is built over the chunk's unique rows (plan_unique_rows)
         // (split-operand dedup: every copy row's image stays in h16 — it is the layer-0
         // residual — and the unique rows' image goes to the idle FFN buffer)
-        HIPTRY(launch_embed_ln(d_tok, sm, c.s0, c.s1, 0, cf.mask_id, cf.vocab, m->word32, m->pos32, m->type32, m->eg, m->eb,
-                               eps, H, o.imgres ? nullptr : t32, o.imgres ? nullptr : xst, dedup && !o.x3s ? nullptr : h16,
-                               kxf, st));
+        // (segment ids, m->type_cur: indexed like d_tok, so a unique row, keyed by hypothesis and
+        // position, has one type and the plan is the same with and without them)
+        HIPTRY(launch_embed_ln(d_tok, m->type_cur, sm, c.s0, c.s1, 0, cf.mask_id, cf.vocab, cf.type_vocab, m->word32,
+                               m->pos32, m->type32, m->eg, m->eb, eps, H, o.imgres ? nullptr : t32,
+                               o.imgres ? nullptr : xst, dedup && !o.x3s ? nullptr : h16, kxf, st));
         if (dedup)
-            HIPTRY(launch_embed_unique(d_tok, sm, c.s0, c.s1, c.urows, cf.mask_id, cf.vocab, m->word32, m->pos32, m->type32,
-                                       m->eg, m->eb, eps, H, o.x3s ? inter : h16, kxf, st));
+            HIPTRY(launch_embed_unique(d_tok, m->type_cur, sm, c.s0, c.s1, c.urows, cf.mask_id, cf.vocab, cf.type_vocab,
+                                       m->word32, m->pos32, m->type32, m->eg, m->eb, eps, H, o.x3s ? inter : h16, kxf,
+                                       st));
         return RS_OK;
     }
 
@@ -827,6 +835,25 @@ struct TopkCall {
     }
 };
 
+// Every entry point that runs the encoder: takes the segment ids left by rs_model_set_token_types
+// (begin: they must cover the call's n_tok tokens) and drops them when the call returns, whatever it
+// returns, so the setting never outlives one call.
+struct TypeCall {
+    rs_model* m;
+    explicit TypeCall(rs_model* m_) : m(m_) {}
+    ~TypeCall() {
+        if (m) { m->type_next = nullptr; m->type_n = 0; m->type_cur = nullptr; }
+    }
+    int begin(int64_t n_tok) {
+        if (!m->type_next) return RS_OK;
+        if (m->type_n != n_tok)
+            return fail(RS_EARG, "rs_model_set_token_types gave " + std::to_string(m->type_n) +
+                                     " token types, this call addresses " + std::to_string(n_tok) + " tokens");
+        m->type_cur = m->type_next;
+        return RS_OK;
+    }
+};
+
 void prof_collect(rs_model* m) {
     if (m->recs.empty()) return;
     (void)hipEventSynchronize(m->recs.back().b);
@@ -916,7 +943,7 @@ int rs_model_finalize(rs_model* m) {
     } while (0)
     UP32(m->word32, word, V * H);
     UP32(m->pos32, pos, (size_t)c.max_pos * H);
-    UP32(m->type32, typ, H);     // token_type_ids are all 0 (modeling_bert.py:88-94)
+    UP32(m->type32, typ, (size_t)c.type_vocab * H);   // row 0 alone without segment ids (modeling_bert.py:88-94)
     UP32(m->eg, eg, H);
     UP32(m->eb, eb, H);
     m->layers.resize(c.layers);
@@ -1024,9 +1051,11 @@ int rs_model_reserve(rs_model* m, int64_t max_rows) {
 
 int rs_pll_score(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off, int32_t n_hyp,
                  double* d_pll, float* d_row_lp, void* stream) {
+    TypeCall ty(m);
     if (!m || !h_hyp_off || n_hyp < 0 || (n_hyp > 0 && (!d_tok || !d_pll))) return fail(RS_EARG, "null argument");
     hipStream_t st = (hipStream_t)stream;
     if (n_hyp == 0) return RS_OK;
+    if (int r = ty.begin(h_hyp_off[n_hyp])) return r;
     CALL_ORDER(m, st);
     SeqList sl;
     std::vector<int> hso(n_hyp + 1, 0);
@@ -1050,6 +1079,7 @@ int rs_pll_score(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off, in
 int rs_pll_score_spans(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off, int32_t n_hyp,
                        const int32_t* h_row_off, const int32_t* h_lo, const int32_t* h_hi, const int32_t* h_query,
                        double* d_pll, float* d_row_lp, void* stream) {
+    TypeCall ty(m);
     if (!m || !h_hyp_off || !h_row_off || n_hyp < 0 || (n_hyp > 0 && (!d_tok || !d_pll)))
         return fail(RS_EARG, "null argument");
     hipStream_t st = (hipStream_t)stream;
@@ -1058,6 +1088,7 @@ int rs_pll_score_spans(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_o
     for (int h = 0; h < n_hyp; ++h)
         if (h_row_off[h + 1] < h_row_off[h]) return fail(RS_EARG, "row_off not ascending at hypothesis " + std::to_string(h));
     if (h_row_off[n_hyp] > 0 && (!h_lo || !h_hi || !h_query)) return fail(RS_EARG, "null argument");
+    if (int r = ty.begin(h_hyp_off[n_hyp])) return r;
     CALL_ORDER(m, st);
     SeqList sl;
     std::vector<int> hso(h_row_off, h_row_off + n_hyp + 1);     // one sequence per row
@@ -1086,9 +1117,11 @@ int rs_pll_score_spans(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_o
 int rs_masked_logprob(rs_model* m, const int32_t* d_ids, const int32_t* h_seq_off,
                       const int32_t* h_query, const int32_t* d_label, int32_t n_seq, float* d_out,
                       void* stream) {
+    TypeCall ty(m);
     if (!m || !h_seq_off || !h_query || n_seq < 0 || (n_seq > 0 && (!d_ids || !d_label || !d_out)))
         return fail(RS_EARG, "null argument");
     if (n_seq == 0) return RS_OK;
+    if (int r = ty.begin(h_seq_off[n_seq])) return r;
     CALL_ORDER(m, (hipStream_t)stream);
     SeqList sl;
     for (int s = 0; s < n_seq; ++s) {
@@ -1102,10 +1135,12 @@ int rs_masked_logprob(rs_model* m, const int32_t* d_ids, const int32_t* h_seq_of
 
 int rs_masked_topk(rs_model* m, const int32_t* d_ids, const int32_t* h_seq_off, const int32_t* h_query,
                    int32_t n_seq, int32_t k, int32_t* d_top_id, float* d_top_lp, void* stream) {
+    TypeCall ty(m);
     if (!m || !h_seq_off || !h_query || n_seq < 0 || (n_seq > 0 && !d_ids)) return fail(RS_EARG, "null argument");
     TopkCall tk(m);
     if (int r = tk.begin(k, d_top_id, d_top_lp)) return r;
     if (n_seq == 0) return RS_OK;
+    if (int r = ty.begin(h_seq_off[n_seq])) return r;
     hipStream_t st = (hipStream_t)stream;
     CALL_ORDER(m, st);
     SeqList sl;
@@ -1121,10 +1156,12 @@ int rs_masked_topk(rs_model* m, const int32_t* d_ids, const int32_t* h_seq_off, 
 
 int rs_pll_topk(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off, int32_t n_hyp, int32_t k,
                 double* d_pll, float* d_row_lp, int32_t* d_top_id, float* d_top_lp, void* stream) {
+    TypeCall ty(m);
     if (!m || !h_hyp_off || n_hyp < 0 || (n_hyp > 0 && !d_tok)) return fail(RS_EARG, "null argument");
     TopkCall tk(m);
     if (int r = tk.begin(k, d_top_id, d_top_lp)) return r;
     if (n_hyp == 0) return RS_OK;
+    if (int r = ty.begin(h_hyp_off[n_hyp])) return r;
     hipStream_t st = (hipStream_t)stream;
     CALL_ORDER(m, st);
     SeqList sl;
@@ -1149,8 +1186,10 @@ int rs_pll_topk(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off, int
 
 int rs_cls_score(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off, int32_t n_hyp,
                  float* d_out, void* stream) {
+    TypeCall ty(m);
     if (!m || !h_hyp_off || n_hyp < 0 || (n_hyp > 0 && (!d_tok || !d_out))) return fail(RS_EARG, "null argument");
     if (n_hyp == 0) return RS_OK;
+    if (int r = ty.begin(h_hyp_off[n_hyp])) return r;
     CALL_ORDER(m, (hipStream_t)stream);
     SeqList sl;
     for (int h = 0; h < n_hyp; ++h) {
@@ -1164,8 +1203,10 @@ int rs_cls_score(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off, in
 
 int rs_token_embed(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off, int32_t n_hyp,
                    void* d_emb, void* stream) {
+    TypeCall ty(m);
     if (!m || !h_hyp_off || n_hyp < 0 || (n_hyp > 0 && (!d_tok || !d_emb))) return fail(RS_EARG, "null argument");
     if (n_hyp == 0) return RS_OK;
+    if (int r = ty.begin(h_hyp_off[n_hyp])) return r;
     CALL_ORDER(m, (hipStream_t)stream);
     SeqList sl;
     for (int h = 0; h < n_hyp; ++h) {
@@ -1185,6 +1226,7 @@ int rs_token_embed(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off, 
 
 int rs_bertscore_recall(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off,
                         const int32_t* h_utt_off, int32_t n_utt, float* d_rmat, float* d_rmat0, void* stream) {
+    TypeCall ty(m);          // (the ids are taken by the rs_token_embed call below)
     if (!m || !h_hyp_off || !h_utt_off || n_utt < 0 || (n_utt > 0 && (!d_tok || !d_rmat)))
         return fail(RS_EARG, "null argument");
     if (n_utt == 0) return RS_OK;
@@ -1235,6 +1277,14 @@ int rs_bertscore_recall(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_
     LAUNCH_OTHER(launch_bertscore_recall(m->emb.as<f16>(), H, d + w_items + w_moff, d + w_items + w_moff + n_hyp + 1,
                                          (const long long*)(d + w_items), (const int4*)d, n_items, d_rmat, d_rmat0, st,
                                          two));
+    return RS_OK;
+}
+
+int rs_model_set_token_types(rs_model* m, const int32_t* d_type, int64_t n) {
+    if (!m) return fail(RS_EARG, "null model");
+    if (d_type && n < 0) return fail(RS_EARG, "negative count");
+    m->type_next = d_type;
+    m->type_n = d_type ? n : 0;
     return RS_OK;
 }
 

@@ -62,9 +62,10 @@ hipError_t tr_dropout(float* dst, const float* src, long long n, const TrDrop& d
 hipError_t tr_dropout_keep(uint8_t* keep, long long n, const TrDrop& d, hipStream_t s);
 
 // h0 = drop(LN(x0)) (site 0); x0 and its statistics saved pre-dropout
-hipError_t tr_embed_ln(const int* row_tok, const int* row_pos, int M, int vocab, const float* word,
-                       const float* pos, const float* type0, const float* g, const float* b, float eps, int H,
-                       float* x0, float2* st, float* h0, hipStream_t s, const TrDrop& d = TrDrop());
+// row_type (nullable): per-row segment id into typetab [type_vocab, H] (clamped); without: row 0
+hipError_t tr_embed_ln(const int* row_tok, const int* row_pos, const int* row_type, int M, int vocab, int type_vocab,
+                       const float* word, const float* pos, const float* typetab, const float* g, const float* b,
+                       float eps, int H, float* x0, float2* st, float* h0, hipStream_t s, const TrDrop& d = TrDrop());
 // y <- drop(y + bias) + res (saved), h = LN(y); bias == nullptr: plain LN of y (no dropout)
 hipError_t tr_bias_res_ln(float* y, const float* bias, const float* res, int M, const float* g, const float* b,
                           float eps, int H, float2* st, float* h, hipStream_t s, const TrDrop& d = TrDrop());
@@ -89,8 +90,9 @@ hipError_t tr_attn_bwd_tiled(const float* qkv, const float* P, const float* dctx
 hipError_t tr_ln_bwd(const float* dy, const float* x, const float2* st, const float* g, float* dx, int M, int H,
                      hipStream_t s);
 size_t tr_colsum_scratch(int M, int N);
+// rtype (nullable): row predicate, the sum runs over the rows with rtype[r] == want, in the same order
 hipError_t tr_colsum(const float* dy, const float* x, const float2* st, int M, int N, int mode, float* part,
-                     float* out, int accumulate, hipStream_t s);
+                     float* out, int accumulate, hipStream_t s, const int* rtype = nullptr, int want = 0);
 hipError_t tr_colsum_ln(const float* dy, const float* x, const float2* st, int M, int N, float* part, float* out_g,
                         float* out_b, hipStream_t s);
 hipError_t tr_word_grad(const float* dx0, const int* utok, const int* toff, const int* rows, int n_uniq, int H,

@@ -97,7 +97,10 @@ struct rs_trainer {
     Buf act, grad, meta, small, ws;   // ws: split-K partials of tr_sgemm
     long long step = 0;
     uint64_t drop_step = 0;         // dropout-step counter (key of the next dropout-active step)
-    std::vector<int> h_tok, h_meta;
+    std::vector<int> h_tok, h_meta, h_type;
+    // rs_trainer_set_token_types: segment ids of the next step, [type_n] device ints (null: all 0)
+    const int32_t* type_next = nullptr;
+    int64_t type_n = 0;
 };
 
 namespace {
@@ -331,6 +334,8 @@ struct StepCtx {
     const long long* pofs = nullptr;
     const int* seq = nullptr;
     size_t i_tok = 0, i_pos = 0, i_aux = 0, i_utok = 0, i_toff = 0, i_ord = 0, i_klen = 0;
+    size_t i_type = 0;              // row types column (0: the step has no segment ids)
+    const int* row_type() const { return i_type ? dm + i_type : nullptr; }
     float* x0 = nullptr;
     float2* st0 = nullptr;
     struct LA { float *hin, *qkv, *P, *ctx, *x1, *h1, *pre, *act, *x2; float2 *st1, *st2; };
@@ -357,6 +362,20 @@ struct StepCtx {
     }
 };
 
+// A training step takes the segment ids left by rs_trainer_set_token_types and drops the setting
+// when it returns, whatever it returns (the scorer's TypeCall).
+struct TypeStep {
+    rs_trainer* t;
+    const int32_t* d_type = nullptr;
+    int64_t n = 0;
+    explicit TypeStep(rs_trainer* t_) : t(t_) {
+        if (t) { d_type = t->type_next; n = t->type_n; }
+    }
+    ~TypeStep() {
+        if (t) { t->type_next = nullptr; t->type_n = 0; }
+    }
+};
+
 uint32_t drop_thresh(float p) { return p <= 0.f ? 0u : (uint32_t)std::min(4294967295.0, (double)p * 4294967296.0); }
 
 // train mode (the reference's model.train() under grad_update) with p > 0: this step's key
@@ -375,14 +394,18 @@ int set_dropout(StepCtx& c, const rs_train_opts* o) {
 
 // host metadata + buffers.  aux: extra int32 array uploaded with the metadata (utt_off);
 // h_klen (nullable): per-sequence key lengths (padded-batch rows, rs_train_step_mlm).
-int prepare(StepCtx& c, const int32_t* d_tok, const int32_t* h_off, int n_seq, const std::vector<int>& aux,
-            const int32_t* h_klen = nullptr) {
+// ty: the step's segment ids (d_type null: none), one per token row.
+int prepare(StepCtx& c, const TypeStep& ty, const int32_t* d_tok, const int32_t* h_off, int n_seq,
+            const std::vector<int>& aux, const int32_t* h_klen = nullptr) {
     rs_trainer* t = c.t;
     const rs_bert_cfg& cf = t->cfg;
     const int H = cf.hidden, F = cf.intermediate, nh = cf.heads, NL = cf.layers;
     if (n_seq <= 0 || h_off[0] != 0) return rs_fail(RS_EARG, "empty batch or offsets not starting at 0");
     c.S = n_seq;
     c.M = h_off[n_seq];
+    if (ty.d_type && ty.n != c.M)
+        return rs_fail(RS_EARG, "rs_trainer_set_token_types gave " + std::to_string(ty.n) +
+                                    " token types, this step addresses " + std::to_string(c.M) + " tokens");
     for (int s = 0; s < n_seq; ++s) {
         const int T = h_off[s + 1] - h_off[s];
         if (T < 1) return rs_fail(RS_EARG, "empty sequence");
@@ -404,7 +427,10 @@ int prepare(StepCtx& c, const int32_t* d_tok, const int32_t* h_off, int n_seq, c
     TRY_BLAS(rocblas_set_stream(t->blas, st));
     t->h_tok.resize(M);
     TRY_HIP(hipMemcpyAsync(t->h_tok.data(), d_tok, (size_t)M * 4, hipMemcpyDeviceToHost, st));
+    t->h_type.resize(ty.d_type ? M : 0);
+    if (ty.d_type) TRY_HIP(hipMemcpyAsync(t->h_type.data(), ty.d_type, (size_t)M * 4, hipMemcpyDeviceToHost, st));
     TRY_HIP(hipStreamSynchronize(st));
+    for (int& k : t->h_type) k = std::min(std::max(k, 0), cf.type_vocab - 1);   // clamped like token ids
     std::vector<int> row_pos(M), order(M);
     for (int s = 0; s < S; ++s)
         for (int r = h_off[s]; r < h_off[s + 1]; ++r) row_pos[r] = r - h_off[s];
@@ -426,7 +452,7 @@ int prepare(StepCtx& c, const int32_t* d_tok, const int32_t* h_off, int n_seq, c
         const long long T = h_off[s + 1] - h_off[s];
         pofs[s + 1] = pofs[s] + (long long)nh * T * T;
     }
-    // int layout: pofs (int64) | row_tok | row_pos | seq_off | aux | utok | toff | order | klen
+    // int layout: pofs (int64) | row_tok | row_pos | seq_off | aux | utok | toff | order | klen | row_type
     std::vector<int>& hm = t->h_meta;
     hm.assign(2 * (S + 1), 0);
     std::memcpy(hm.data(), pofs.data(), (S + 1) * 8);
@@ -448,6 +474,11 @@ int prepare(StepCtx& c, const int32_t* d_tok, const int32_t* h_off, int n_seq, c
     if (h_klen) {
         c.i_klen = hm.size();
         hm.insert(hm.end(), h_klen, h_klen + S);
+    }
+    c.i_type = 0;
+    if (ty.d_type) {
+        c.i_type = hm.size();
+        hm.insert(hm.end(), t->h_type.begin(), t->h_type.end());
     }
     TRY_ALLOC(t->meta.ensure(hm.size() * 4));
     TRY_HIP(hipMemcpyAsync(t->meta.p, hm.data(), hm.size() * 4, hipMemcpyHostToDevice, st));
@@ -517,8 +548,9 @@ int encoder_forward(StepCtx& c) {
     const int H = cf.hidden, F = cf.intermediate, nh = cf.heads, M = c.M;
     float* Pm = t->P.f();
     hipStream_t st = c.st;
-    TRY_HIP(tr_embed_ln(c.dm + c.i_tok, c.dm + c.i_pos, M, cf.vocab, Pm + t->o_word, Pm + t->o_pos, Pm + t->o_type,
-                        Pm + t->o_eg, Pm + t->o_eb, cf.ln_eps, H, c.x0, c.st0, c.la[0].hin, st, c.drop(0, false)));
+    TRY_HIP(tr_embed_ln(c.dm + c.i_tok, c.dm + c.i_pos, c.row_type(), M, cf.vocab, cf.type_vocab, Pm + t->o_word,
+                        Pm + t->o_pos, Pm + t->o_type, Pm + t->o_eg, Pm + t->o_eb, cf.ln_eps, H, c.x0, c.st0, c.la[0].hin,
+                        st, c.drop(0, false)));
     for (int l = 0; l < cf.layers; ++l) {
         const TLayer& L = t->lay[l];
         StepCtx::LA& a = c.la[l];
@@ -601,7 +633,13 @@ int encoder_backward(StepCtx& c) {
     // word embeddings: += (the tied MLM decoder already wrote its part)
     TRY_HIP(tr_word_grad(dB, c.dm + c.i_utok, c.dm + c.i_toff, c.dm + c.i_ord, c.n_uniq, H, Gm + t->o_word, st));
     TRY_HIP(tr_pos_grad(dB, c.seq, c.S, c.tmax, H, Gm + t->o_pos, st));
-    TRY_HIP(tr_colsum(dB, nullptr, nullptr, M, H, 0, part, Gm + t->o_type, 0, st));  // token_type row 0
+    // token types: without segment ids every row into row 0 (the other rows stay 0 from the step's
+    // memset); with them, row k from the rows of type k, one predicated pass per type
+    if (!c.row_type())
+        TRY_HIP(tr_colsum(dB, nullptr, nullptr, M, H, 0, part, Gm + t->o_type, 0, st));
+    else
+        for (int k = 0; k < cf.type_vocab; ++k)
+            TRY_HIP(tr_colsum(dB, nullptr, nullptr, M, H, 0, part, Gm + t->o_type + (size_t)k * H, 0, st, c.row_type(), k));
     return RS_OK;
 }
 
@@ -625,6 +663,7 @@ extern "C" {
 int rs_train_step_cls(rs_trainer* t, const int32_t* d_tok, const int32_t* h_hyp_off, int32_t n_hyp,
                       const int32_t* h_utt_off, int32_t n_utt, const float* d_target, const float* d_am,
                       const float* d_err, const rs_train_opts* o, float* d_scores, float* d_loss, void* stream) {
+    TypeStep ty(t);
     if (!t || !h_hyp_off || !h_utt_off || !o || !d_loss || n_hyp <= 0 || n_utt <= 0 || !d_tok || !d_target)
         return rs_fail(RS_EARG, "null argument / empty batch");
     if (!t->finalized) return rs_fail(RS_ESTATE, "rs_trainer_finalize not called");
@@ -638,7 +677,7 @@ int rs_train_step_cls(rs_trainer* t, const int32_t* d_tok, const int32_t* h_hyp_
     c.t = t;
     c.st = (hipStream_t)stream;
     if (int r = set_dropout(c, o)) return r;
-    if (int r = prepare(c, d_tok, h_hyp_off, n_hyp, std::vector<int>(h_utt_off, h_utt_off + n_utt + 1))) return r;
+    if (int r = prepare(c, ty, d_tok, h_hyp_off, n_hyp, std::vector<int>(h_utt_off, h_utt_off + n_utt + 1))) return r;
     if (int r = encoder_forward(c)) return r;
     const int H = t->cfg.hidden, S = c.S;
     float *Pm = t->P.f(), *Gm = t->G.f();
@@ -668,6 +707,7 @@ int rs_train_step_cls(rs_trainer* t, const int32_t* d_tok, const int32_t* h_hyp_
 int rs_train_step_mlm(rs_trainer* t, const int32_t* d_ids, const int32_t* h_seq_off, int32_t n_seq,
                       const int32_t* h_key_len, const int32_t* d_labels, const rs_train_opts* o, float* d_loss,
                       void* stream) {
+    TypeStep ty(t);
     if (!t || !h_seq_off || !o || !d_loss || n_seq <= 0 || !d_ids || !d_labels)
         return rs_fail(RS_EARG, "null argument / empty batch");
     if (!t->finalized) return rs_fail(RS_ESTATE, "rs_trainer_finalize not called");
@@ -676,7 +716,7 @@ int rs_train_step_mlm(rs_trainer* t, const int32_t* d_ids, const int32_t* h_seq_
     c.t = t;
     c.st = (hipStream_t)stream;
     if (int r = set_dropout(c, o)) return r;
-    if (int r = prepare(c, d_ids, h_seq_off, n_seq, {}, h_key_len)) return r;
+    if (int r = prepare(c, ty, d_ids, h_seq_off, n_seq, {}, h_key_len)) return r;
     if (int r = encoder_forward(c)) return r;
     const rs_bert_cfg& cf = t->cfg;
     const int H = cf.hidden, V = cf.vocab, M = c.M;
@@ -722,6 +762,14 @@ int rs_trainer_reset_optimizer(rs_trainer* t) {
     TRY_HIP(hipMemset(t->M1.p, 0, t->n_params * 4));
     TRY_HIP(hipMemset(t->V1.p, 0, t->n_params * 4));
     t->step = 0;
+    return RS_OK;
+}
+
+int rs_trainer_set_token_types(rs_trainer* t, const int32_t* d_type, int64_t n) {
+    if (!t) return rs_fail(RS_EARG, "null trainer");
+    if (d_type && n < 0) return rs_fail(RS_EARG, "negative count");
+    t->type_next = d_type;
+    t->type_n = d_type ? n : 0;
     return RS_OK;
 }
 

@@ -35,6 +35,8 @@ class NBest:
     hyp_ids: List[str]
     lens: Optional[np.ndarray] = None   # per-hypothesis len(text) when built from text
     word_start: Optional[np.ndarray] = None   # uint8 [sum T]: 1 where a word begins (``pll_spans``)
+    token_type: Optional[np.ndarray] = None   # uint8 [sum T]: segment id per token (``with_context``)
+    score_from: Optional[np.ndarray] = None   # int32 [H]: first scored position of a hypothesis
 
     @property
     def n_hyp(self) -> int:
@@ -67,16 +69,24 @@ class NBest:
                      np.asarray(self.am[h0:h1], np.float64), list(self.refs[u0:u1]),
                      list(self.utt_ids[u0:u1]), list(self.hyp_ids[h0:h1]),
                      word_start=None if self.word_start is None
-                     else np.ascontiguousarray(self.word_start[t0:t1], np.uint8))
+                     else np.ascontiguousarray(self.word_start[t0:t1], np.uint8),
+                     token_type=None if self.token_type is None
+                     else np.ascontiguousarray(self.token_type[t0:t1], np.uint8),
+                     score_from=None if self.score_from is None
+                     else np.ascontiguousarray(self.score_from[h0:h1], np.int32))
 
     def subset(self, utts: Sequence[int]) -> "NBest":
-        toks, hoff, uoff, am, hyp_ids, refs, uids, ws = [], [0], [0], [], [], [], [], []
+        toks, hoff, uoff, am, hyp_ids, refs, uids, ws, tt, sf = [], [0], [0], [], [], [], [], [], [], []
         for u in utts:
             for h in range(self.utt_off[u], self.utt_off[u + 1]):
                 seg = self.tokens[self.hyp_off[h]:self.hyp_off[h + 1]]
                 toks.append(seg)
                 if self.word_start is not None:
                     ws.append(self.word_start[self.hyp_off[h]:self.hyp_off[h + 1]])
+                if self.token_type is not None:
+                    tt.append(self.token_type[self.hyp_off[h]:self.hyp_off[h + 1]])
+                if self.score_from is not None:
+                    sf.append(self.score_from[h])
                 hoff.append(hoff[-1] + len(seg))
                 am.append(self.am[h])
                 hyp_ids.append(self.hyp_ids[h])
@@ -87,13 +97,16 @@ class NBest:
                      np.asarray(hoff, np.int32), np.asarray(uoff, np.int32),
                      np.asarray(am, np.float64), refs, uids, hyp_ids,
                      word_start=None if self.word_start is None
-                     else (np.concatenate(ws).astype(np.uint8) if ws else np.zeros(0, np.uint8)))
+                     else (np.concatenate(ws).astype(np.uint8) if ws else np.zeros(0, np.uint8)),
+                     token_type=None if self.token_type is None
+                     else (np.concatenate(tt).astype(np.uint8) if tt else np.zeros(0, np.uint8)),
+                     score_from=None if self.score_from is None else np.asarray(sf, np.int32))
 
 
 PLL_VARIANTS = ("original", "word_l2r", "whole_word")
 
 
-def pll_spans(hyp_off, word_start, variant: str = "original"):
+def pll_spans(hyp_off, word_start, variant: str = "original", score_from=None):
     """Rows of ``rs_pll_score_spans`` for a PLL variant: per hypothesis L = T - 2 rows, row p
     (p = 1..L, in order) scored at ``query = p`` with positions ``[lo, hi)`` masked.
 
@@ -104,8 +117,10 @@ def pll_spans(hyp_off, word_start, variant: str = "original"):
 
     ``word_start``: uint8 per token, 1 where a word begins ([CLS] and [SEP] are 1; the first
     word piece of a hypothesis begins a word whatever its flag says).  ``None`` is allowed for
-    ``"original"`` only.  Returns int32 arrays ``(row_off [H + 1], lo, hi, query)``, positions
-    relative to the hypothesis."""
+    ``"original"`` only.  ``score_from`` (int per hypothesis, ``with_context``): hypothesis h keeps
+    only its rows with ``p >= score_from[h]``, the tail of the unrestricted rows (a context in front
+    is attended to and never scored).  Returns int32 arrays ``(row_off [H + 1], lo, hi, query)``,
+    positions relative to the hypothesis."""
     if variant not in PLL_VARIANTS:
         raise ValueError(f"unknown PLL variant {variant!r} {PLL_VARIANTS}")
     off = np.asarray(hyp_off, np.int64)
@@ -134,7 +149,70 @@ def pll_spans(hyp_off, word_start, variant: str = "original"):
         k = np.searchsorted(starts, g, side="right")     # starts[k - 1] <= g < starts[k]
         hi = starts[k] - off[hyp]
         lo = p if variant == "word_l2r" else starts[k - 1] - off[hyp]
-    return (row_off.astype(np.int32), np.asarray(lo, np.int32), np.asarray(hi, np.int32), p.astype(np.int32))
+    lo, hi = np.asarray(lo), np.asarray(hi)
+    if score_from is not None:
+        sf = np.asarray(score_from, np.int64)
+        if len(sf) != len(L):
+            raise ValueError("score_from must have one entry per hypothesis")
+        keep = p >= sf[hyp]
+        row_off = np.zeros(len(off), np.int64)
+        row_off[1:] = np.cumsum(np.bincount(hyp[keep], minlength=len(L)))
+        lo, hi, p = lo[keep], hi[keep], p[keep]
+    return (row_off.astype(np.int32), lo.astype(np.int32), hi.astype(np.int32), p.astype(np.int32))
+
+
+def with_context(tokens, hyp_off, utt_off, ctx_tokens, ctx_off, max_len: int = 512, word_start=None,
+                 ctx_word_start=None):
+    """Sentence pairs ``[CLS] ctx_u [SEP] w_1..w_L [SEP]`` for every hypothesis of utterance u: the
+    input BERT was pre-trained on, with the context (previous transcript, prompt, first-pass
+    hypothesis) as segment 0 and the hypothesis as segment 1.
+
+    ``tokens`` / ``hyp_off`` / ``utt_off``: the ``NBest`` layout (``[CLS] w.. [SEP]`` rows).
+    ``ctx_tokens`` / ``ctx_off``: one ragged bare id list per utterance (no [CLS] / [SEP]).  An
+    utterance with an empty context keeps its rows as they are (types 0, ``score_from`` 1).  A pair
+    longer than ``max_len`` drops context tokens from the left (the oldest); a hypothesis that does
+    not fit on its own (``L + 3 > max_len``) raises ``ValueError``.  ``word_start`` (uint8 per
+    token) is carried over with ``ctx_word_start`` (uint8 per context token; None: every context
+    token begins a word); the middle [SEP] and ``w_1`` begin words.
+
+    Returns ``(tokens int32, hyp_off int32, token_type uint8, score_from int32, word_start uint8 or
+    None)``; ``score_from[h]`` is the pair-relative position of ``w_1``."""
+    tok = np.asarray(tokens, np.int32)
+    off, uoff, coff = (np.asarray(a, np.int64) for a in (hyp_off, utt_off, ctx_off))
+    ctx = np.asarray(ctx_tokens, np.int32)
+    if len(coff) != len(uoff):
+        raise ValueError("ctx_off must have one entry per utterance plus one")
+    ws = None if word_start is None else np.asarray(word_start, np.uint8)
+    cws = np.ones(len(ctx), np.uint8) if ctx_word_start is None else np.asarray(ctx_word_start, np.uint8)
+    o_tok, o_type, o_ws, o_off, o_from = [], [], [], [0], []
+    for u in range(len(uoff) - 1):
+        c0, c1 = int(coff[u]), int(coff[u + 1])
+        for h in range(int(uoff[u]), int(uoff[u + 1])):
+            a, b = int(off[h]), int(off[h + 1])
+            L = b - a - 2
+            if L + 3 > max_len:
+                raise ValueError(f"hypothesis {h} does not fit beside a context ({L} + 3 > max_len {max_len})")
+            k0 = max(c0, c1 - (max_len - (L + 3)))         # left truncation: the newest context stays
+            if c1 == c0:
+                o_tok.append(tok[a:b])
+                o_type.append(np.zeros(b - a, np.uint8))
+                if ws is not None:
+                    o_ws.append(ws[a:b])
+                o_from.append(1)
+            else:
+                n_ctx = c1 - k0
+                o_tok.append(np.concatenate([tok[a:a + 1], ctx[k0:c1], [SEP_ID], tok[a + 1:b]]).astype(np.int32))
+                o_type.append(np.concatenate([np.zeros(n_ctx + 2, np.uint8), np.ones(L + 1, np.uint8)]))
+                if ws is not None:
+                    row = np.concatenate([ws[a:a + 1], cws[k0:c1], [1], ws[a + 1:b]]).astype(np.uint8)
+                    if L > 0:
+                        row[n_ctx + 2] = 1
+                    o_ws.append(row)
+                o_from.append(n_ctx + 2)
+            o_off.append(o_off[-1] + len(o_tok[-1]))
+    cat = lambda xs, dt: np.concatenate(xs).astype(dt) if xs else np.zeros(0, dt)
+    return (cat(o_tok, np.int32), np.asarray(o_off, np.int32), cat(o_type, np.uint8), np.asarray(o_from, np.int32),
+            None if ws is None else cat(o_ws, np.uint8))
 
 
 def from_lists(hyps: List[List[Sequence[int]]], am: Optional[List[List[float]]] = None,

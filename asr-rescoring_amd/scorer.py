@@ -111,6 +111,37 @@ class BertEngine:
             return tokens.to(self.device, torch.int32).contiguous()
         return torch.from_numpy(np.ascontiguousarray(tokens, np.int32)).to(self.device)
 
+    # ---- segment ids (rs_model_set_token_types) ----------------------------------------
+    def _set_types(self, token_types):
+        """Hands ``token_types`` (one segment id per token of the NEXT scoring call, array or tensor;
+        None: nothing set, every token type 0) to the handle.  Values outside ``[0, type_vocab)``
+        raise ``ValueError`` here (the device would clamp them); a length that differs from the
+        call's token count makes that call fail (RS_EARG).  Returns the device tensor, which the
+        caller keeps alive until its call has returned."""
+        if token_types is None:
+            return None
+        d_type = self._dev_tokens(token_types).reshape(-1)
+        if d_type.numel():
+            lo, hi = int(d_type.min()), int(d_type.max())
+            if lo < 0 or hi >= self.shape.type_vocab:
+                raise ValueError(f"token types must be in [0, {self.shape.type_vocab}), got {lo if lo < 0 else hi}")
+        _lib.check(self.lib.rs_model_set_token_types(self.handle, _lib.ptr(d_type), d_type.numel()))
+        return d_type
+
+    def clear_token_types(self):
+        """Drops a pending segment-id setting (``rs_model_set_token_types(NULL)``)."""
+        _lib.check(self.lib.rs_model_set_token_types(self.handle, None, 0))
+
+
+def _padded_types(token_type_ids, keep: torch.Tensor):
+    """Ragged copy of a padded [B, T] ``token_type_ids`` batch, gathered like ``input_ids``."""
+    if token_type_ids is None:
+        return None
+    tt = token_type_ids.to(keep.device)
+    if tt.shape != keep.shape:
+        raise ValueError("token_type_ids must have the shape of input_ids")
+    return tt[keep].to(torch.int32).contiguous()
+
 
 class PLLScorer(BertEngine):
     """MLM_PLL scorer (BertForMaskedLM head)."""
@@ -121,34 +152,43 @@ class PLLScorer(BertEngine):
         # BertForMaskedLM; "fp16" is an opt-in reduced-precision fast mode
         super().__init__(weights, shape, _lib.RS_HEAD_MLM, device, max_rows, precision)
 
-    def score_nbest(self, tokens, hyp_off, return_rows: bool = False, variant: str = "original", word_start=None):
+    def score_nbest(self, tokens, hyp_off, return_rows: bool = False, variant: str = "original", word_start=None,
+                    token_types=None, score_from=None):
         """tokens int32 [sum T] ([CLS] w.. [SEP] per hypothesis), hyp_off int [H+1].
 
         ``variant``: "original" (``rs_pll_score``), or "word_l2r" / "whole_word" (``data.pll_spans``
         over ``word_start``, uint8 per token, through ``score_spans``).
 
+        ``token_types``: one segment id per token (``data.with_context``: 0 over ``[CLS] context
+        [SEP]``, 1 over the hypothesis).  ``score_from`` int [H]: hypothesis h is scored only at
+        positions ``p >= score_from[h]`` (the hypothesis half of a pair); every variant then goes
+        through ``score_spans``.
+
         Returns float64 [H] device tensor of PLL (and float32 per-row log-probs)."""
-        if variant != "original":
-            if variant not in PLL_VARIANTS:
-                raise ValueError(f"unknown PLL variant {variant!r} {PLL_VARIANTS}")
-            if word_start is None:
+        if variant not in PLL_VARIANTS:
+            raise ValueError(f"unknown PLL variant {variant!r} {PLL_VARIANTS}")
+        if variant != "original" or score_from is not None:
+            if variant != "original" and word_start is None:
                 raise ValueError(f"variant {variant!r} needs word_start")
-            return self.score_spans(tokens, hyp_off, *pll_spans(hyp_off, word_start, variant), return_rows=return_rows)
+            return self.score_spans(tokens, hyp_off, *pll_spans(hyp_off, word_start, variant, score_from=score_from),
+                                    return_rows=return_rows, token_types=token_types)
         off = np.ascontiguousarray(hyp_off, np.int32)
         n_hyp = len(off) - 1
         d_tok = self._dev_tokens(tokens)
         n_rows = int((np.diff(off) - 2).sum()) if n_hyp else 0
         pll = torch.empty(n_hyp, dtype=torch.float64, device=self.device)
         rows = torch.empty(n_rows, dtype=torch.float32, device=self.device) if return_rows else None
+        d_type = self._set_types(token_types)      # noqa: F841  (alive until the call has returned)
         _lib.check(self.lib.rs_pll_score(self.handle, _lib.ptr(d_tok), off.ctypes.data, n_hyp,
                                          _lib.ptr(pll), _lib.ptr(rows), _lib.stream_ptr(self.device)))
         return (pll, rows) if return_rows else pll
 
-    def score_spans(self, tokens, hyp_off, row_off, lo, hi, query, return_rows: bool = False):
+    def score_spans(self, tokens, hyp_off, row_off, lo, hi, query, return_rows: bool = False, token_types=None):
         """Span-masked PLL (``rs_pll_score_spans``): row r of hypothesis h (``row_off[h] <= r <
         row_off[h + 1]``) is the hypothesis with positions ``[lo[r], hi[r])`` replaced by [MASK],
         scored at ``query[r]`` (positions relative to the hypothesis, ``1 <= lo <= query < hi <=
-        T - 1``).  Rows may come in any order, repeat and skip positions.
+        T - 1``).  Rows may come in any order, repeat and skip positions.  ``token_types``: one
+        segment id per token (``score_nbest``).
 
         Returns float64 [H] device tensor (sum of each hypothesis' rows in row order; no rows: 0)
         and, with ``return_rows``, the float32 per-row log-probs."""
@@ -164,19 +204,22 @@ class PLLScorer(BertEngine):
         d_tok = self._dev_tokens(tokens)
         pll = torch.empty(n_hyp, dtype=torch.float64, device=self.device)
         rows = torch.empty(n_rows, dtype=torch.float32, device=self.device) if return_rows else None
+        d_type = self._set_types(token_types)      # noqa: F841
         _lib.check(self.lib.rs_pll_score_spans(self.handle, _lib.ptr(d_tok), off.ctypes.data, n_hyp, roff.ctypes.data,
                                                *[_lib.ptr(c) for c in cols], _lib.ptr(pll), _lib.ptr(rows),
                                                _lib.stream_ptr(self.device)))
         return (pll, rows) if return_rows else pll
 
     def score(self, nb: NBest) -> np.ndarray:
-        return self.score_nbest(nb.tokens, nb.hyp_off).cpu().numpy()
+        return self.score_nbest(nb.tokens, nb.hyp_off, token_types=nb.token_type,
+                                score_from=nb.score_from).cpu().numpy()
 
     def masked_logprob(self, input_ids: torch.Tensor, attention_mask: torch.Tensor,
-                       labels: torch.Tensor, mask_pos) -> torch.Tensor:
+                       labels: torch.Tensor, mask_pos, token_type_ids=None) -> torch.Tensor:
         """``token_score`` of MLM_PLL/main.py:101-105 for a padded batch [B, T].
 
-        ``attention_mask`` rows must be a prefix of ones (``pad_sequence`` output)."""
+        ``attention_mask`` rows must be a prefix of ones (``pad_sequence`` output);
+        ``token_type_ids``: padded [B, T] segment ids as transformers takes them."""
         lens = _prefix_lengths(attention_mask)
         B = input_ids.shape[0]
         mp = np.asarray([int(x) for x in mask_pos], np.int32)
@@ -191,16 +234,19 @@ class PLLScorer(BertEngine):
                                      torch.from_numpy(mp.astype(np.int64)).to(self.device)]
         lab = lab.to(torch.int32).contiguous()
         out = torch.empty(B, dtype=torch.float32, device=self.device)
+        d_type = self._set_types(_padded_types(token_type_ids, keep))      # noqa: F841
         _lib.check(self.lib.rs_masked_logprob(self.handle, _lib.ptr(d_ids), off.ctypes.data,
                                               mp.ctypes.data, _lib.ptr(lab), B, _lib.ptr(out),
                                               _lib.stream_ptr(self.device)))
         return out
 
-    def masked_topk(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, mask_pos, k: int = 5):
+    def masked_topk(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, mask_pos, k: int = 5,
+                    token_type_ids=None):
         """The model's ``k`` preferred tokens at ``mask_pos`` of every row of a padded batch [B, T]
         (the form ``masked_logprob`` takes): ``torch.topk(log_softmax(logits[range(B), mask_pos]), k)``
         of MLM_PLL/main.py:101-105 without the [B, vocab] rows.  Returns device tensors
-        (ids int32 [B, k], logprob float32 [B, k]), best first, equal logits by the lower id."""
+        (ids int32 [B, k], logprob float32 [B, k]), best first, equal logits by the lower id.
+        ``token_type_ids``: padded [B, T] segment ids."""
         lens = _prefix_lengths(attention_mask)
         B = input_ids.shape[0]
         mp = np.asarray([int(x) for x in mask_pos], np.int32)
@@ -212,11 +258,12 @@ class PLLScorer(BertEngine):
         off[1:] = np.cumsum(lens)
         top_id = torch.empty((B, max(int(k), 0)), dtype=torch.int32, device=self.device)
         top_lp = torch.empty((B, max(int(k), 0)), dtype=torch.float32, device=self.device)
+        d_type = self._set_types(_padded_types(token_type_ids, keep))      # noqa: F841
         _lib.check(self.lib.rs_masked_topk(self.handle, _lib.ptr(d_ids), off.ctypes.data, mp.ctypes.data, B, int(k),
                                            _lib.ptr(top_id), _lib.ptr(top_lp), _lib.stream_ptr(self.device)))
         return top_id, top_lp
 
-    def topk_nbest(self, tokens, hyp_off, k: int = 5, return_pll: bool = False):
+    def topk_nbest(self, tokens, hyp_off, k: int = 5, return_pll: bool = False, token_types=None):
         """``score_nbest`` plus the ``k`` preferred tokens of every masked row (rows ordered as
         ``score_nbest(..., return_rows=True)``'s: hypothesis by hypothesis, position by position).
 
@@ -230,6 +277,7 @@ class PLLScorer(BertEngine):
         rows = torch.empty(n_rows, dtype=torch.float32, device=self.device) if return_pll else None
         top_id = torch.empty((n_rows, max(int(k), 0)), dtype=torch.int32, device=self.device)
         top_lp = torch.empty((n_rows, max(int(k), 0)), dtype=torch.float32, device=self.device)
+        d_type = self._set_types(token_types)      # noqa: F841
         _lib.check(self.lib.rs_pll_topk(self.handle, _lib.ptr(d_tok), off.ctypes.data, n_hyp, int(k), _lib.ptr(pll),
                                         _lib.ptr(rows), _lib.ptr(top_id), _lib.ptr(top_lp),
                                         _lib.stream_ptr(self.device)))
@@ -269,17 +317,18 @@ class RescoreBertScorer(BertEngine):
                  precision: str = "fp16x3"):
         super().__init__(weights, shape, _lib.RS_HEAD_CLS, device, max_rows, precision)
 
-    def score_nbest(self, tokens, hyp_off) -> torch.Tensor:
+    def score_nbest(self, tokens, hyp_off, token_types=None) -> torch.Tensor:
         off = np.ascontiguousarray(hyp_off, np.int32)
         n = len(off) - 1
         d_tok = self._dev_tokens(tokens)
         out = torch.empty(n, dtype=torch.float32, device=self.device)
+        d_type = self._set_types(token_types)      # noqa: F841
         _lib.check(self.lib.rs_cls_score(self.handle, _lib.ptr(d_tok), off.ctypes.data, n,
                                          _lib.ptr(out), _lib.stream_ptr(self.device)))
         return out
 
     def score(self, nb: NBest) -> np.ndarray:
-        return self.score_nbest(nb.tokens, nb.hyp_off).cpu().numpy()
+        return self.score_nbest(nb.tokens, nb.hyp_off, token_types=nb.token_type).cpu().numpy()
 
 
 class RescoreBertHIP(torch.nn.Module):
@@ -293,7 +342,7 @@ class RescoreBertHIP(torch.nn.Module):
         super().__init__()
         self.engine = RescoreBertScorer(weights, shape, device, max_rows, precision)
 
-    def forward(self, input_ids: torch.Tensor, attention_mask: torch.Tensor) -> torch.Tensor:
+    def forward(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, token_type_ids=None) -> torch.Tensor:
         lens = _prefix_lengths(attention_mask)
         if (lens == 0).any():
             raise ValueError("every row needs at least one attended token")
@@ -303,7 +352,7 @@ class RescoreBertHIP(torch.nn.Module):
         keep = torch.arange(T, device=dev)[None, :] < torch.from_numpy(lens).to(dev)[:, None]
         off = np.zeros(len(lens) + 1, np.int32)
         off[1:] = np.cumsum(lens)
-        return self.engine.score_nbest(ids[keep].to(torch.int32), off)
+        return self.engine.score_nbest(ids[keep].to(torch.int32), off, token_types=_padded_types(token_type_ids, keep))
 
 
 def pll_of(weights, nb: NBest, shape: BertShape = BERT_BASE, device=0) -> np.ndarray:

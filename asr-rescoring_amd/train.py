@@ -134,6 +134,22 @@ class _Trainer:
         inside every run_one_epoch (RescoreBert/main.py:83-86, MLM_PLL/main.py:74-77)."""
         _lib.check(self.lib.rs_trainer_reset_optimizer(self.handle))
 
+    def _set_types(self, token_types, n_tok: int):
+        """Segment ids of the NEXT step (``rs_trainer_set_token_types``): one per token row, values
+        in ``[0, type_vocab)`` (``ValueError`` otherwise).  Returns the device tensor, which the
+        caller keeps alive until the step has returned."""
+        if token_types is None:
+            return None
+        tt = np.ascontiguousarray(np.asarray(token_types).reshape(-1), np.int32)
+        if len(tt) != n_tok:
+            raise ValueError(f"token_types needs one entry per token ({n_tok}), got {len(tt)}")
+        tv = self.shape.type_vocab
+        if len(tt) and (tt.min() < 0 or tt.max() >= tv):
+            raise ValueError(f"token types must be in [0, {tv})")
+        d_type = torch.as_tensor(tt).to(self.device)
+        _lib.check(self.lib.rs_trainer_set_token_types(self.handle, _lib.ptr(d_type), len(tt)))
+        return d_type
+
     @staticmethod
     def _update_flag(update) -> int:
         """True: backward + AdamW step; False: backward only; "loss": forward + loss only."""
@@ -166,12 +182,13 @@ class _Trainer:
 class RescoreBertTrainer(_Trainer):
     HEAD = "cls"
 
-    def step(self, tokens, hyp_off, utt_off, target, am=None, cer=None, update=True
+    def step(self, tokens, hyp_off, utt_off, target, am=None, cer=None, update=True, token_types=None
              ) -> Tuple[float, np.ndarray]:
         """One step on a batch (RescoreBert/main.py:98-154): ``utt_off`` groups the hypotheses
         (``reference_groups``), ``target`` = mlm_pll_score, ``am`` = hyps_am_score, ``cer`` =
         hyps_cer.  ``update``: True (backward + AdamW), False (gradients only) or "loss"
-        (forward only).  Returns (loss, CLS scores before the update)."""
+        (forward only).  ``token_types``: one segment id per token (``data.with_context`` pairs).
+        Returns (loss, CLS scores before the update)."""
         hoff = np.ascontiguousarray(hyp_off, np.int32)
         uoff = np.ascontiguousarray(utt_off, np.int32)
         n = len(hoff) - 1
@@ -182,6 +199,7 @@ class RescoreBertTrainer(_Trainer):
         sc = torch.empty(n, dtype=torch.float32, device=dev)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         self.opts.update = self._update_flag(update)
+        d_type = self._set_types(token_types, int(hoff[-1]))      # noqa: F841
         _lib.check(self.lib.rs_train_step_cls(self.handle, _lib.ptr(d_tok), hoff.ctypes.data, n, uoff.ctypes.data,
                                               len(uoff) - 1, _lib.ptr(d_t), _lib.ptr(d_am), _lib.ptr(d_err),
                                               ctypes.byref(self.opts), _lib.ptr(sc), _lib.ptr(loss),
@@ -212,10 +230,11 @@ def reference_groups(n_rows: int, n_best: int) -> np.ndarray:
     return np.arange(0, n_rows + 1, n_best, dtype=np.int32)
 
 
-def pad_rows(seqs: Sequence[Sequence[int]], labels: Sequence[Sequence[int]]):
+def pad_rows(seqs: Sequence[Sequence[int]], labels: Sequence[Sequence[int]], types=None):
     """The reference's MLM batch (collate, MLM_PLL/main.py:28-54): every row padded to the
     batch's longest with id 0 and label 0 (pad_sequence); the attention mask's zeros become
-    key lengths.  Returns (ids, row_off, labels, key_len) as int32."""
+    key lengths.  Returns (ids, row_off, labels, key_len) as int32, and with ``types`` (a segment-id
+    row per sequence) a fifth item, the types padded with 0 like the ids."""
     T = max(len(x) for x in seqs)
     n = len(seqs)
     ids = np.zeros((n, T), np.int32)
@@ -225,7 +244,13 @@ def pad_rows(seqs: Sequence[Sequence[int]], labels: Sequence[Sequence[int]]):
         ids[i, :len(x)] = x
         lab[i, :len(y)] = y
         klen[i] = len(x)
-    return ids.ravel(), np.arange(0, n * T + 1, T, dtype=np.int32), lab.ravel(), klen
+    out = (ids.ravel(), np.arange(0, n * T + 1, T, dtype=np.int32), lab.ravel(), klen)
+    if types is None:
+        return out
+    tt = np.zeros((n, T), np.int32)
+    for i, t in enumerate(types):
+        tt[i, :len(t)] = t
+    return out + (tt.ravel(),)
 
 
 class MLMTrainer(_Trainer):
@@ -234,7 +259,7 @@ class MLMTrainer(_Trainer):
     it the rows are ragged and every position is real."""
     HEAD = "mlm"
 
-    def step(self, ids, seq_off, labels, key_len=None, update=True) -> float:
+    def step(self, ids, seq_off, labels, key_len=None, update=True, token_types=None) -> float:
         off = np.ascontiguousarray(seq_off, np.int32)
         kl = None if key_len is None else np.ascontiguousarray(key_len, np.int32)
         if kl is not None and len(kl) != len(off) - 1:
@@ -244,6 +269,7 @@ class MLMTrainer(_Trainer):
         d_lab = torch.as_tensor(np.ascontiguousarray(labels, np.int32)).to(dev)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         self.opts.update = self._update_flag(update)
+        d_type = self._set_types(token_types, int(off[-1]))      # noqa: F841
         _lib.check(self.lib.rs_train_step_mlm(self.handle, _lib.ptr(d_ids), off.ctypes.data, len(off) - 1,
                                               None if kl is None else kl.ctypes.data, _lib.ptr(d_lab),
                                               ctypes.byref(self.opts), _lib.ptr(loss), _lib.stream_ptr(dev)))
@@ -251,14 +277,15 @@ class MLMTrainer(_Trainer):
 
 
 def rescorebert_epoch(tr: RescoreBertTrainer, tokens, hyp_off, target, am, cer, batch_size: int, n_best: int,
-                      update=True) -> float:
+                      update=True, token_types=None) -> float:
     """One pass of RescoreBert/main.py:82-163 run_one_epoch(train=True) over the hypotheses in
     order: batches of ``batch_size * n_best`` rows (set_dataloader :71-79, shuffle False),
     groups of ``n_best`` (``reference_groups``) for MD_MWER / MD_MWED, which reshape the batch
     to (-1, n_best) (RescoreBert/main.py:116,132); MD is a plain MSELoss(sum) over the batch
     (:104-110) and takes any batch, ragged last batch and short N-best lists included;
     ``update`` True = grad_update (the caller resets AdamW first, as the reference builds it per
-    call), "loss" = the dev pass.  Returns the epoch loss (mean of the batch losses)."""
+    call), "loss" = the dev pass.  ``token_types``: per-token segment ids, sliced with the tokens.
+    Returns the epoch loss (mean of the batch losses)."""
     hoff = np.asarray(hyp_off, np.int64)
     n = len(hoff) - 1
     rows = batch_size * n_best
@@ -268,23 +295,26 @@ def rescorebert_epoch(tr: RescoreBertTrainer, tokens, hyp_off, target, am, cer, 
         t0, t1 = int(hoff[b0]), int(hoff[b1])
         groups = np.array([0, b1 - b0], np.int32) if tr.method == "MD" else reference_groups(b1 - b0, n_best)
         loss, _ = tr.step(np.asarray(tokens[t0:t1]), (hoff[b0:b1 + 1] - t0).astype(np.int32),
-                          groups, target[b0:b1], am[b0:b1], cer[b0:b1], update=update)
+                          groups, target[b0:b1], am[b0:b1], cer[b0:b1], update=update,
+                          token_types=None if token_types is None else np.asarray(token_types[t0:t1]))
         tot += loss
         nb += 1
     return tot / max(nb, 1)
 
 
 def mlm_epoch(tr: MLMTrainer, seqs: Sequence[Sequence[int]], labels: Sequence[Sequence[int]], batch_size: int,
-              update=True, order=None) -> float:
+              update=True, order=None, token_types=None) -> float:
     """One pass of MLM_PLL/main.py:73-114 run_one_epoch (do_scoring False) over do_job rows:
     batches of ``batch_size`` rows (in ``order``, default as given), padded as the reference's
-    collate pads them (``pad_rows``).  Returns the epoch loss (mean of the batch losses)."""
+    collate pads them (``pad_rows``).  ``token_types``: a segment-id row per sequence, padded with
+    the ids.  Returns the epoch loss (mean of the batch losses)."""
     idx = np.arange(len(seqs)) if order is None else np.asarray(order)
     tot, nb = 0.0, 0
     for b0 in range(0, len(idx), batch_size):
         sel = idx[b0:b0 + batch_size]
-        ids, off, lab, klen = pad_rows([seqs[i] for i in sel], [labels[i] for i in sel])
-        tot += tr.step(ids, off, lab, klen, update=update)
+        tt = None if token_types is None else [token_types[i] for i in sel]
+        ids, off, lab, klen, *typ = pad_rows([seqs[i] for i in sel], [labels[i] for i in sel], tt)
+        tot += tr.step(ids, off, lab, klen, update=update, token_types=typ[0] if typ else None)
         nb += 1
     return tot / max(nb, 1)
 

@@ -132,6 +132,24 @@ int rs_model_reserve(rs_model* m, int64_t max_rows);
 int rs_model_set_sync_check(rs_model* m, int on);
 int rs_check(rs_model* m, void* stream);
 
+/* Segment ids (transformers token_type_ids) for the NEXT scoring call on this handle:
+ * d_type int32 [n] device, d_type[i] = type of d_tok[i] / d_ids[i] of that call.
+ * Reference seam: BertEmbeddings (modeling_bert.py:53-108) with token_type_ids as
+ * Nbest_Align/model.py:21-26 passes them: row = word[id] + token_type[type] + position[t]; a
+ * [MASK] row of the PLL calls takes the type of the position it stands at.
+ * One-shot: the setting applies to the next call that runs the encoder (rs_pll_score,
+ * rs_pll_score_spans, rs_masked_logprob, rs_masked_topk, rs_pll_topk, rs_cls_score, rs_token_embed,
+ * rs_bertscore_recall) and is cleared when that call returns, whatever it returns (a call with
+ * n_hyp == 0 consumes it as well).  d_type == NULL clears a pending setting.  d_type must stay valid
+ * until that call's work on its stream is complete, like d_tok.
+ * The consuming call fails with RS_EARG when n differs from the number of tokens it addresses
+ * (h_off[n_seq]).  Values outside [0, type_vocab) are clamped on the device, like token ids, and never
+ * read out of bounds.  Without a setting every row has type 0 and scores are those of a handle that
+ * never heard of segment ids, bit for bit.  Precision modes, chunking, layer-0 dedup (a unique row is
+ * keyed by hypothesis and position, and so is its type), the last-layer query path, the range guard,
+ * deferred checks and call ordering are unchanged. */
+int rs_model_set_token_types(rs_model* m, const int32_t* d_type, int64_t n);
+
 /* MLM_PLL scoring (MLM_PLL/preprocess.py:9-30 + MLM_PLL/main.py:83-107):
  *   d_tok      int32 [h_hyp_off[n_hyp]]  hypotheses as [CLS] w_1..w_L [SEP]
  *   h_hyp_off  int32 [n_hyp + 1]         host offsets into d_tok (T_h = L_h + 2 >= 3)
@@ -356,6 +374,14 @@ int rs_train_step_cls(rs_trainer* t, const int32_t* d_tok, const int32_t* h_hyp_
 int rs_train_step_mlm(rs_trainer* t, const int32_t* d_ids, const int32_t* h_seq_off, int32_t n_seq,
                       const int32_t* h_key_len, const int32_t* d_labels, const rs_train_opts* opts,
                       float* d_loss, void* stream);
+/* Segment ids (token_type_ids) of the NEXT rs_train_step_cls / rs_train_step_mlm: d_type int32 [n]
+ * device, one per token row of that step (n must equal its h_off[n_seq], else the step fails with
+ * RS_EARG).  One-shot like rs_model_set_token_types: cleared when that step returns, whatever it
+ * returns; d_type == NULL clears a pending setting; values are clamped to [0, type_vocab).
+ * The gradient of token_type_embeddings.weight[k] is the column sum of the embedding gradient over
+ * the rows of type k, in the fixed row order of every other column sum (no atomics; a type without
+ * rows gets exactly 0).  With nothing set the step is unchanged, bit for bit (all rows into row 0). */
+int rs_trainer_set_token_types(rs_trainer* t, const int32_t* d_type, int64_t n);
 /* The dropout-step counter: the key the next dropout-active step uses (then incremented). */
 int64_t rs_trainer_dropout_step(const rs_trainer* t);
 /* Sets it (0 .. 2^63-1; a 64-bit counter whose high word is a Philox counter word and low word
