@@ -11,6 +11,7 @@ from __future__ import annotations
 import ctypes
 import os
 
+import numpy as np
 import torch  # noqa: F401  (must load torch's HIP runtime before librescore.so)
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -173,6 +174,22 @@ def load(path: str = LIB_PATH):
 def check(rc: int) -> None:
     if rc != 0:
         raise RescoreError(f"librescore error {rc}: {load().rs_last_error().decode()}")
+
+
+def bert_cfg(shape, heads: int, precision: str = "fp16") -> RsBertCfg:
+    """``rs_bert_cfg`` of a ``weights.BertShape`` with a head mask and a precision mode."""
+    return RsBertCfg(shape.vocab, shape.hidden, shape.layers, shape.heads, shape.intermediate, shape.max_pos,
+                     shape.type_vocab, shape.ln_eps, shape.mask_id, heads, RS_PREC[precision])
+
+
+def upload_tensors(fn, handle, weights, keys=None) -> None:
+    """``fn`` (``rs_model_set_tensor`` / ``rs_trainer_set_tensor``) on every tensor of the HF-keyed
+    ``weights`` (only those in ``keys``, when given), as contiguous float32."""
+    for k, v in weights.items():
+        if keys is not None and k not in keys:
+            continue
+        a = np.ascontiguousarray(v, dtype=np.float32)
+        check(fn(handle, k.encode(), a.ctypes.data, 0, (ctypes.c_int64 * a.ndim)(*a.shape), a.ndim))
 
 
 def ptr(t) -> int:

@@ -77,14 +77,13 @@ class BertScorer(BertEngine):
         """[sum T, H]: L2-normalised last hidden state of every token — float32 (hi + lo/64 of
         the two-part image) in the fp16x3 mode, fp16 in the fp16 mode.  ``token_types``: one
         segment id per token."""
-        off = np.ascontiguousarray(hyp_off, np.int32)
-        d_tok = self._dev_tokens(tokens)
+        d_tok, off, n_hyp = self._hyps(tokens, hyp_off)
         H, two = self.shape.hidden, self.precision == "fp16x3"
         out = torch.empty(int(off[-1]) if len(off) else 0, H * (2 if two else 1), dtype=torch.float16,
                           device=self.device)
         d_type = self._set_types(token_types)      # noqa: F841
-        _lib.check(self.lib.rs_token_embed(self.handle, _lib.ptr(d_tok), off.ctypes.data, len(off) - 1,
-                                           _lib.ptr(out), _lib.stream_ptr(self.device)))
+        _lib.check(self.lib.rs_token_embed(self.handle, _lib.ptr(d_tok), off.ctypes.data, n_hyp, _lib.ptr(out),
+                                           _lib.stream_ptr(self.device)))
         if two:
             return out[:, :H].float() + out[:, H:].float() * (1.0 / 64.0)
         return out
@@ -92,12 +91,11 @@ class BertScorer(BertEngine):
     def recall_matrices(self, tokens, hyp_off, utt_off, clamped: bool = True):
         """Concatenated n_u x n_u float32 blocks R[i, j] = R(cand i | ref j), the same with every
         token maximum clamped at 0 (None unless ``clamped``), and the block offsets."""
-        hoff = np.ascontiguousarray(hyp_off, np.int32)
+        d_tok, hoff, _ = self._hyps(tokens, hyp_off)
         uoff = np.ascontiguousarray(utt_off, np.int32)
         n_u = np.diff(uoff).astype(np.int64)
         moff = np.zeros(len(uoff), np.int64)
         moff[1:] = np.cumsum(n_u * n_u)
-        d_tok = self._dev_tokens(tokens)
         rmat = torch.empty(int(moff[-1]), dtype=torch.float32, device=self.device)
         rmat0 = torch.empty_like(rmat) if clamped else None
         _lib.check(self.lib.rs_bertscore_recall(self.handle, _lib.ptr(d_tok), hoff.ctypes.data, uoff.ctypes.data,

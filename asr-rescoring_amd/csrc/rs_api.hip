@@ -15,7 +15,7 @@
 
 #include "common.h"
 #include "seq_plan.h"
-#include "../../include/rescore.h"
+#include "host_util.h"
 
 namespace {
 
@@ -25,33 +25,6 @@ int fail(int code, const std::string& msg) {
     g_err = msg;
     return code;
 }
-
-#define HIPTRY(expr)                                                                   \
-    do {                                                                               \
-        hipError_t e_ = (expr);                                                        \
-        if (e_ != hipSuccess)                                                          \
-            return fail(RS_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
-    } while (0)
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    hipError_t ensure(size_t n) {
-        if (n <= bytes) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-        hipError_t e = hipMalloc(&p, n);
-        if (e == hipSuccess) bytes = n;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
-    template <class T> T* as() const { return (T*)p; }
-};
 
 struct Layer {
     f16 *wqkv, *wo, *w1, *w2;       // operand images of the precision mode (kx parts, planar)
@@ -116,18 +89,11 @@ struct rs_model {
                                 // zeroed by every launch), sticky statistics-wait timeout flag
     DevBuf ctxq, resq, tq32, hq32, hq16, interq, lab, llog, part, rowlp_tmp;
     DevBuf meta;
-    f16* emb_dst = nullptr;     // MODE_EMB output (rs_token_embed / rs_bertscore_recall)
-    // rs_masked_topk / rs_pll_topk (TopkCall): k != 0 makes head_mlm run the top-k decoder form into
-    // the call's outputs [sequence, k]; the candidate workspace exists from the first such call on
-    int topk_k = 0;
-    int32_t* topk_id = nullptr;
-    float* topk_lp = nullptr;
-    DevBuf topk_cand;           // topk_cand_bytes(vpad)
-    // rs_model_set_token_types (TypeCall): segment ids of the next encoder call, [type_n] device ints
-    // parallel to its tokens; type_cur: the ids of the call that is running (null: every row type 0)
+    DevBuf topk_cand;           // top-k calls (topk_begin): topk_cand_bytes(vpad), from the first such call on
+    // rs_model_set_token_types: segment ids pending for the next encoder call, [type_n] device ints
+    // parallel to its tokens (PendingTypes hands them to that call and clears them)
     const int32_t* type_next = nullptr;
     int64_t type_n = 0;
-    const int32_t* type_cur = nullptr;
     DevBuf emb, plan;           // rs_bertscore_recall: token embeddings, work-item plan
     DevBuf flag;                // non-finite-output flag of the last scoring call(s) (range guard)
     bool sync_check = true;     // scoring calls synchronise and report their flags (rs_model_set_sync_check)
@@ -241,16 +207,16 @@ __global__ void __launch_bounds__(256) nonfinite_kernel(const T* __restrict__ v,
 // Reads the flags (non-finite output, statistics-wait timeout) after synchronising the stream,
 // clears them and turns them into the call's error.
 int report_flags(rs_model* m, hipStream_t st, const char* what) {
-    if (!m->pinned_flag) HIPTRY(hipHostMalloc((void**)&m->pinned_flag, 8, hipHostMallocDefault));
+    if (!m->pinned_flag) TRY_HIP(hipHostMalloc((void**)&m->pinned_flag, 8, hipHostMallocDefault));
     m->pinned_flag[0] = 0;
     m->pinned_flag[1] = 0;
-    if (m->flag.p) HIPTRY(hipMemcpyAsync(m->pinned_flag, m->flag.p, 4, hipMemcpyDeviceToHost, st));
-    if (m->lnerr.p) HIPTRY(hipMemcpyAsync(m->pinned_flag + 1, m->lnerr.p, 4, hipMemcpyDeviceToHost, st));
-    HIPTRY(hipStreamSynchronize(st));
+    if (m->flag.p) TRY_HIP(hipMemcpyAsync(m->pinned_flag, m->flag.p, 4, hipMemcpyDeviceToHost, st));
+    if (m->lnerr.p) TRY_HIP(hipMemcpyAsync(m->pinned_flag + 1, m->lnerr.p, 4, hipMemcpyDeviceToHost, st));
+    TRY_HIP(hipStreamSynchronize(st));
     const int bad = m->pinned_flag[0], lnto = m->pinned_flag[1];
-    if (bad && m->flag.p) HIPTRY(hipMemset(m->flag.p, 0, 4));
+    if (bad && m->flag.p) TRY_HIP(hipMemset(m->flag.p, 0, 4));
     if (lnto) {
-        HIPTRY(hipMemset(m->lnerr.p, 0, 4));
+        TRY_HIP(hipMemset(m->lnerr.p, 0, 4));
         return fail(RS_EHIP, "a residual-LayerNorm GEMM timed out waiting for its row statistics "
                              "(set RS_LNFUSE=0 to use the separate LayerNorm pass)");
     }
@@ -269,13 +235,13 @@ int report_flags(rs_model* m, hipStream_t st, const char* what) {
 template <class T>
 int mark_nonfinite(rs_model* m, hipStream_t st, const T* p, size_t n) {
     if (!m->flag.p) {
-        HIPTRY(m->flag.ensure(4));
-        HIPTRY(hipMemset(m->flag.p, 0, 4));
+        TRY_HIP(m->flag.ensure(4));
+        TRY_HIP(hipMemset(m->flag.p, 0, 4));
     }
     if (n > 0) {
         const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 2048);
         hipLaunchKernelGGL(nonfinite_kernel<T>, dim3(blocks), dim3(256), 0, st, p, n, m->flag.as<int>());
-        HIPTRY(hipGetLastError());
+        TRY_HIP(hipGetLastError());
     }
     return RS_OK;
 }
@@ -289,8 +255,8 @@ int check_finite(rs_model* m, hipStream_t st, const T* p, size_t n, const char* 
 // Start of every scoring call in synchronous mode: a timeout flag left by an earlier call that
 // failed before its report is dropped (each call reports only its own).
 int begin_call(rs_model* m, hipStream_t st) {
-    if (m->sync_check && m->lnerr.p) HIPTRY(hipMemsetAsync(m->lnerr.p, 0, 4, st));
-    if (m->sync_check && m->flag.p) HIPTRY(hipMemsetAsync(m->flag.p, 0, 4, st));
+    if (m->sync_check && m->lnerr.p) TRY_HIP(hipMemsetAsync(m->lnerr.p, 0, 4, st));
+    if (m->sync_check && m->flag.p) TRY_HIP(hipMemsetAsync(m->flag.p, 0, 4, st));
     return RS_OK;
 }
 
@@ -308,7 +274,7 @@ int order_begin(rs_model* m, hipStream_t st) {
                              "failed): cross-stream ordering was lost; synchronise the device and retry");
     }
     if (m->have_last && st != m->last_stream && m->call_done)
-        HIPTRY(hipStreamWaitEvent(st, m->call_done, 0));
+        TRY_HIP(hipStreamWaitEvent(st, m->call_done, 0));
     return RS_OK;
 }
 struct CallOrder {
@@ -327,7 +293,7 @@ struct CallOrder {
 };
 // Opening of every entry point that enqueues work: the model's device, then the call ordering.
 #define CALL_ORDER(m_, st_)                                   \
-    HIPTRY(hipSetDevice(m_->device));                         \
+    TRY_HIP(hipSetDevice(m_->device));                         \
     if (int r_ = order_begin((m_), (st_))) return r_;         \
     CallOrder order_((m_), (st_))
 
@@ -346,42 +312,42 @@ int reserve_impl(rs_model* m, int64_t max_rows) {
     m->s_cap = (int)(max_rows / 3) + 1;
     m->r_pad = pad_rows(m->s_cap);
     const size_t M = m->m_pad, R = m->r_pad, H = c.hidden, F = c.intermediate;
-    HIPTRY(hipSetDevice(m->device));
+    TRY_HIP(hipSetDevice(m->device));
     const size_t kx = m->kx;
-    HIPTRY(m->xst.ensure(M * sizeof(float2)));
-    HIPTRY(m->xst1.ensure(M * sizeof(float2)));
-    HIPTRY(m->lnx.ensure(lnres_granules((int)M) * 8));
-    HIPTRY(hipMemset(m->lnx.p, 0, m->lnx.bytes));               // granule tags start at 0 (never a launch's)
+    TRY_HIP(m->xst.ensure(M * sizeof(float2)));
+    TRY_HIP(m->xst1.ensure(M * sizeof(float2)));
+    TRY_HIP(m->lnx.ensure(lnres_granules((int)M) * 8));
+    TRY_HIP(hipMemset(m->lnx.p, 0, m->lnx.bytes));               // granule tags start at 0 (never a launch's)
     if (!m->lncnt.p) {
-        HIPTRY(m->lncnt.ensure(lnres_counter_bytes()));
-        HIPTRY(hipMemset(m->lncnt.p, 0, m->lncnt.bytes));
+        TRY_HIP(m->lncnt.ensure(lnres_counter_bytes()));
+        TRY_HIP(hipMemset(m->lncnt.p, 0, m->lncnt.bytes));
     }
-    HIPTRY(m->lnerr.ensure(16));
-    HIPTRY(hipMemset(m->lnerr.p, 0, 16));
-    HIPTRY(m->h16.ensure(M * H * 2 * kx));
-    HIPTRY(m->t32.ensure(M * H * 4));
-    HIPTRY(m->qkv.ensure(M * 3 * H * (kx == 3 ? 4 : 2)));
-    HIPTRY(m->ctx.ensure(M * H * 2 * kx));
-    HIPTRY(m->inter.ensure(M * F * 2 * kx));
-    HIPTRY(m->ctxq.ensure(R * H * 2 * kx));
-    HIPTRY(m->resq.ensure(R * H * 4));
-    HIPTRY(m->tq32.ensure(R * H * 4));
-    HIPTRY(m->hq32.ensure(R * H * 4));
-    HIPTRY(m->hq16.ensure(R * H * 2 * kx));
-    HIPTRY(m->interq.ensure(R * F * 2 * kx));
-    HIPTRY(m->lab.ensure(R * 4));
-    HIPTRY(m->llog.ensure(R * 4));
-    if (c.heads_mask & RS_HEAD_MLM) HIPTRY(m->part.ensure(R * (size_t)(m->vpad / 64) * sizeof(float2)));
+    TRY_HIP(m->lnerr.ensure(16));
+    TRY_HIP(hipMemset(m->lnerr.p, 0, 16));
+    TRY_HIP(m->h16.ensure(M * H * 2 * kx));
+    TRY_HIP(m->t32.ensure(M * H * 4));
+    TRY_HIP(m->qkv.ensure(M * 3 * H * (kx == 3 ? 4 : 2)));
+    TRY_HIP(m->ctx.ensure(M * H * 2 * kx));
+    TRY_HIP(m->inter.ensure(M * F * 2 * kx));
+    TRY_HIP(m->ctxq.ensure(R * H * 2 * kx));
+    TRY_HIP(m->resq.ensure(R * H * 4));
+    TRY_HIP(m->tq32.ensure(R * H * 4));
+    TRY_HIP(m->hq32.ensure(R * H * 4));
+    TRY_HIP(m->hq16.ensure(R * H * 2 * kx));
+    TRY_HIP(m->interq.ensure(R * F * 2 * kx));
+    TRY_HIP(m->lab.ensure(R * 4));
+    TRY_HIP(m->llog.ensure(R * 4));
+    if (c.heads_mask & RS_HEAD_MLM) TRY_HIP(m->part.ensure(R * (size_t)(m->vpad / 64) * sizeof(float2)));
     // zero the padded activations once: GEMMs read pad rows (never stored back)
-    HIPTRY(hipMemset(m->h16.p, 0, m->h16.bytes));
-    HIPTRY(hipMemset(m->ctx.p, 0, m->ctx.bytes));
-    HIPTRY(hipMemset(m->inter.p, 0, m->inter.bytes));
-    HIPTRY(hipMemset(m->ctxq.p, 0, m->ctxq.bytes));
-    HIPTRY(hipMemset(m->hq16.p, 0, m->hq16.bytes));
-    HIPTRY(hipMemset(m->interq.p, 0, m->interq.bytes));
-    HIPTRY(hipMemset(m->t32.p, 0, m->t32.bytes));    // pad rows of the residual stream stay finite
-    HIPTRY(hipMemset(m->xst.p, 0, m->xst.bytes));
-    HIPTRY(hipMemset(m->xst1.p, 0, m->xst1.bytes));
+    TRY_HIP(hipMemset(m->h16.p, 0, m->h16.bytes));
+    TRY_HIP(hipMemset(m->ctx.p, 0, m->ctx.bytes));
+    TRY_HIP(hipMemset(m->inter.p, 0, m->inter.bytes));
+    TRY_HIP(hipMemset(m->ctxq.p, 0, m->ctxq.bytes));
+    TRY_HIP(hipMemset(m->hq16.p, 0, m->hq16.bytes));
+    TRY_HIP(hipMemset(m->interq.p, 0, m->interq.bytes));
+    TRY_HIP(hipMemset(m->t32.p, 0, m->t32.bytes));    // pad rows of the residual stream stay finite
+    TRY_HIP(hipMemset(m->xst.p, 0, m->xst.bytes));
+    TRY_HIP(hipMemset(m->xst1.p, 0, m->xst1.bytes));
     return RS_OK;
 }
 
@@ -432,10 +398,27 @@ struct ProfScope {
 };
 
 // One launch under a profile scope of its own, no flops recorded (m, st: the caller's).
-#define LAUNCH(kind_, call_) do { ProfScope ps_(m, st, (kind_), 0); HIPTRY(call_); } while (0)
+#define LAUNCH(kind_, call_) do { ProfScope ps_(m, st, (kind_), 0); TRY_HIP(call_); } while (0)
 #define LAUNCH_OTHER(call_) LAUNCH(RS_K_OTHER, call_)
 
 enum Mode { MODE_MLM = 0, MODE_CLS = 1, MODE_EMB = 2 };
+
+// What one encoder call fixes.  Every entry point builds one on its stack; run_all and ChunkCtx read
+// it and nothing call-scoped from the handle, so no return path has anything to put back.
+struct Call {
+    int mode;
+    const int* d_tok;
+    float* out_rows = nullptr;                // MLM / CLS: one float per sequence
+    const int* d_label = nullptr;             // device labels in place of the sequence list's column
+    const int32_t* d_type = nullptr;          // segment ids parallel to d_tok (null: every row type 0)
+    const std::vector<int>* extra = nullptr;  // extra ints of the metadata upload (e.g. hypothesis ->
+    int** d_extra = nullptr;                  // sequence offsets), and where their device copy lands
+    f16* emb_dst = nullptr;                   // MODE_EMB output
+    // top-k request (topk_begin): k != 0 makes head_mlm run the top-k decoder form into [sequence, k]
+    int topk_k = 0;
+    int32_t* topk_id = nullptr;
+    float* topk_lp = nullptr;
+};
 
 // The environment switches of one scoring call: read once (call_opts, at the top of run_all) and
 // passed down, so that the chunk cap, the dedup plan and the chunk runner see the same resolved
@@ -498,15 +481,14 @@ CallOpts call_opts(const rs_model* m) {
 }
 
 // One chunk's run of the encoder + head over sequences [c.s0, c.s1): what the call fixed, and the
-// typed workspace pointers.  Aggregate: the first seven members are given, the rest follow.
+// typed workspace pointers.  Aggregate: the first six members are given, the rest follow.
 struct ChunkCtx {
     rs_model* m;
     hipStream_t st;
-    const int* d_tok;
+    const Call& call;
     const SeqMeta& sm;
     const Chunk& c;
     const CallOpts& o;
-    int mode;
     const rs_bert_cfg& cf = m->cfg;
     const int H = cf.hidden, F = cf.intermediate, nh = cf.heads, kx = m->kx;
     const float eps = cf.ln_eps;
@@ -531,8 +513,8 @@ struct ChunkCtx {
              int n_flop_cols) {
         ep.m_valid = m_valid;
         ProfScope ps(m, st, kind, 2.0 * m_valid * (double)n_flop_cols * (split ? 3.0 * K : K));
-        if (split) HIPTRY(launch_gemm_x3s(epi, A, W, 2 * K, pad_rows(m_valid), N_pad, K, ep, st));
-        else HIPTRY(launch_gemm(epi, A, W, pad_rows(m_valid), N_pad, K, ep, st,
+        if (split) TRY_HIP(launch_gemm_x3s(epi, A, W, 2 * K, pad_rows(m_valid), N_pad, K, ep, st));
+        else TRY_HIP(launch_gemm(epi, A, W, pad_rows(m_valid), N_pad, K, ep, st,
                                 kind == RS_K_OPROJ ? 1 : kind == RS_K_FFN2 ? 2 : 0));
         return RS_OK;
     }
@@ -564,15 +546,15 @@ struct ChunkCtx {
         // GEMM operand is built over the chunk's unique rows (plan_unique_rows)
         // (split-operand dedup: every copy row's image stays in h16 — it is the layer-0
         // residual — and the unique rows' image goes to the idle FFN buffer)
-        // (segment ids, m->type_cur: indexed like d_tok, so a unique row, keyed by hypothesis and
+        // (segment ids, call.d_type: indexed like d_tok, so a unique row, keyed by hypothesis and
         // position, has one type and the plan is the same with and without them)
-        HIPTRY(launch_embed_ln(d_tok, m->type_cur, sm, c.s0, c.s1, 0, cf.mask_id, cf.vocab, cf.type_vocab, m->word32,
+        TRY_HIP(launch_embed_ln(call.d_tok, call.d_type, sm, c.s0, c.s1, 0, cf.mask_id, cf.vocab, cf.type_vocab, m->word32,
                                m->pos32, m->type32, m->eg, m->eb, eps, H, o.imgres ? nullptr : t32,
                                o.imgres ? nullptr : xst, dedup && !o.x3s ? nullptr : h16, kxf, st));
         if (dedup)
-            HIPTRY(launch_embed_unique(d_tok, m->type_cur, sm, c.s0, c.s1, c.urows, cf.mask_id, cf.vocab, cf.type_vocab,
-                                       m->word32, m->pos32, m->type32, m->eg, m->eb, eps, H, o.x3s ? inter : h16, kxf,
-                                       st));
+            TRY_HIP(launch_embed_unique(call.d_tok, call.d_type, sm, c.s0, c.s1, c.urows, cf.mask_id, cf.vocab,
+                                       cf.type_vocab, m->word32, m->pos32, m->type32, m->eg, m->eb, eps, H,
+                                       o.x3s ? inter : h16, kxf, st));
         return RS_OK;
     }
 
@@ -686,49 +668,48 @@ struct ChunkCtx {
         return RS_OK;
     }
 
-    int head_mlm(float* d_out_rows) {
+    int head_mlm() {
         if (int r = gemm(RS_K_DECODER, EPI_GELU_F32, false, hq16, m->wt, ns, H, kx * H, bias_ep(m->bt, tq, H), H)) return r;
         LAUNCH_OTHER(launch_ln_rows(tq, ns, m->gt, m->bet, eps, H, hq32, nullptr, hq16, kx, st));
-        const MlmDecoder d{hq16, m->wdec, m->bdec, ns, m->vpad, cf.vocab, kx * H, d_tok, sm, c.s0, m->lab.as<int>(),
-                           m->part.as<float2>(), m->llog.as<float>(), d_out_rows + c.s0};
-        if (m->topk_k) {
+        const MlmDecoder d{hq16, m->wdec, m->bdec, ns, m->vpad, cf.vocab, kx * H, call.d_tok, sm, c.s0, m->lab.as<int>(),
+                           m->part.as<float2>(), m->llog.as<float>(), call.out_rows + c.s0};
+        if (call.topk_k) {
             // the only fork of a top-k call: the decoder launcher (its GEMM runs in n_gemm sub-batches)
-            const int k = m->topk_k, n_gemm = (ns + TOPK_SUB_ROWS - 1) / TOPK_SUB_ROWS;
-            const MlmTopk t{k, m->topk_cand.as<float2>(), m->topk_id + (size_t)c.s0 * k, m->topk_lp + (size_t)c.s0 * k};
-            HIPTRY(launch_mlm_decoder_topk(d, t, st, [&](bool is_gemm, auto&& launch) {
+            const int k = call.topk_k, n_gemm = (ns + TOPK_SUB_ROWS - 1) / TOPK_SUB_ROWS;
+            const MlmTopk t{k, m->topk_cand.as<float2>(), call.topk_id + (size_t)c.s0 * k, call.topk_lp + (size_t)c.s0 * k};
+            TRY_HIP(launch_mlm_decoder_topk(d, t, st, [&](bool is_gemm, auto&& launch) {
                 ProfScope ps(m, st, is_gemm ? RS_K_DECODER : RS_K_OTHER,
                              is_gemm ? 2.0 * ns * (double)cf.vocab * (kx * H) / n_gemm : 0);
                 return launch();
             }));
             return RS_OK;
         }
-        HIPTRY(launch_mlm_decoder(d, st, [&](bool is_gemm, auto&& launch) {
+        TRY_HIP(launch_mlm_decoder(d, st, [&](bool is_gemm, auto&& launch) {
             ProfScope ps(m, st, is_gemm ? RS_K_DECODER : RS_K_OTHER, is_gemm ? 2.0 * ns * (double)cf.vocab * (kx * H) : 0);
             return launch();
         }));
         return RS_OK;
     }
-    int head_cls(float* d_out_rows) {
-        LAUNCH_OTHER(launch_cls_linear(hq32, ns, H, m->wlin, m->blin, d_out_rows + c.s0, st));
+    int head_cls() {
+        LAUNCH_OTHER(launch_cls_linear(hq32, ns, H, m->wlin, m->blin, call.out_rows + c.s0, st));
         return RS_OK;
     }
     int emb_out() {
-        LAUNCH_OTHER(launch_embed_out(t32, xst, prev_g(cf.layers), prev_b(cf.layers), sm, c.s0, c.s1, 0, H, m->emb_dst, st,
-                                      o.imgres ? h16 : nullptr, m->kx == 3));
+        LAUNCH_OTHER(launch_embed_out(t32, xst, prev_g(cf.layers), prev_b(cf.layers), sm, c.s0, c.s1, 0, H, call.emb_dst,
+                                      st, o.imgres ? h16 : nullptr, kx == 3));
         return RS_OK;
     }
-    // d_out_rows: one float per sequence of the call (MLM / CLS modes)
-    int run(float* d_out_rows) {
+    int run() {
         if (int r = embed()) return r;
         for (int li = 0; li < cf.layers; ++li) {
-            const bool last = mode != MODE_EMB && li == cf.layers - 1;   // the scoring modes' last layer
+            const bool last = call.mode != MODE_EMB && li == cf.layers - 1;   // the scoring modes' last layer
             const bool uq = dedup && li == 0;
             const bool qrow = last && !uq && o.lastq;                     // query-row-only Q projection
             if (int r = qkv_proj(li, last, uq, qrow)) return r;
             if (int r = last ? layer_query(li, qrow) : o.x3s ? layer_split(li, uq) : layer_f16(li, uq)) return r;
         }
-        if (mode == MODE_EMB) return emb_out();
-        return mode == MODE_MLM ? head_mlm(d_out_rows) : head_cls(d_out_rows);
+        if (call.mode == MODE_EMB) return emb_out();
+        return call.mode == MODE_MLM ? head_mlm() : head_cls();
     }
 };
 
@@ -774,85 +755,153 @@ void plan_dedup(const rs_model* m, const CallOpts& o, int mode, SeqList& sl, std
 }
 
 // One upload of all metadata through the pinned staging buffer: the nine SeqList columns, then
-// the extra ints (e.g. hypothesis -> sequence offsets; *d_extra); d_label: device labels instead.
-int upload_meta(rs_model* m, hipStream_t st, const SeqList& sl, const std::vector<int>* extra, const int* d_label,
-                SeqMeta* sm, int** d_extra) {
-    const size_t S = sl.size(), n_extra = extra ? extra->size() : 0, n_int = 9 * S + n_extra;
-    HIPTRY(m->stage_meta.begin(n_int));
+// the call's extra ints (-> *call.d_extra); call.d_label: device labels instead of the list's.
+int upload_meta(rs_model* m, hipStream_t st, const Call& call, const SeqList& sl, SeqMeta* sm) {
+    const size_t S = sl.size(), n_extra = call.extra ? call.extra->size() : 0, n_int = 9 * S + n_extra;
+    TRY_HIP(m->stage_meta.begin(n_int));
     int* p = m->stage_meta.p;
     const std::vector<int>* cols[9] = {&sl.tok_off, &sl.len, &sl.mask, &sl.query, &sl.label, &sl.row,
                                        &sl.urow_h, &sl.urow_m, &sl.mask_end};
     for (int k = 0; k < 9; ++k) std::memcpy(p + k * S, cols[k]->data(), S * 4);
-    if (n_extra) std::memcpy(p + 9 * S, extra->data(), n_extra * 4);
-    HIPTRY(m->stage_meta.upload(m->meta, n_int, st));
+    if (n_extra) std::memcpy(p + 9 * S, call.extra->data(), n_extra * 4);
+    TRY_HIP(m->stage_meta.upload(m->meta, n_int, st));
     int* d = m->meta.as<int>();
-    if (d_label) HIPTRY(hipMemcpyAsync(d + 4 * S, d_label, S * 4, hipMemcpyDeviceToDevice, st));
+    if (call.d_label) TRY_HIP(hipMemcpyAsync(d + 4 * S, call.d_label, S * 4, hipMemcpyDeviceToDevice, st));
     *sm = SeqMeta{d, d + S, d + 2 * S, d + 3 * S, d + 4 * S, d + 5 * S, d + 6 * S, d + 7 * S, d + 8 * S};
-    if (d_extra) *d_extra = d + 9 * S;
+    if (call.d_extra) *call.d_extra = d + 9 * S;
     return RS_OK;
 }
 
-// Chunks the sequence list, uploads metadata, runs every chunk.  out_rows: one float per
-// sequence.  Extra int arrays (e.g. hypothesis -> sequence offsets) ride in the same upload.
-int run_all(rs_model* m, hipStream_t st, const int* d_tok, SeqList& sl, int mode, float* out_rows,
-            const std::vector<int>* extra, int** d_extra, const int* d_label = nullptr) {
+// Chunks the call's sequence list, uploads metadata, runs every chunk.
+int run_all(rs_model* m, hipStream_t st, const Call& call, SeqList& sl) {
     const CallOpts opts = call_opts(m);
-    if (int r = validate_call(m, mode)) return r;
+    if (int r = validate_call(m, call.mode)) return r;
     if (m->max_rows == 0)
         if (int r = reserve_impl(m, 65536)) return r;
-    HIPTRY(hipSetDevice(m->device));
+    TRY_HIP(hipSetDevice(m->device));
     if (int r = begin_call(m, st)) return r;
     std::vector<Chunk> chunks;
     if (int r = cut_chunks(m, sl, chunk_cap(m, opts), &chunks)) return r;
-    plan_dedup(m, opts, mode, sl, chunks);
+    plan_dedup(m, opts, call.mode, sl, chunks);
     SeqMeta sm{};
-    if (int r = upload_meta(m, st, sl, extra, d_label, &sm, d_extra)) return r;
+    if (int r = upload_meta(m, st, call, sl, &sm)) return r;
     for (const Chunk& c : chunks) {
-        ChunkCtx cx{m, st, d_tok, sm, c, opts, mode};
-        if (int r = cx.run(out_rows)) return r;
+        ChunkCtx cx{m, st, call, sm, c, opts};
+        if (int r = cx.run()) return r;
     }
     return RS_OK;
 }
 
-// A top-k call: checks k and the outputs, makes sure of the candidate workspace and switches
-// head_mlm to the top-k decoder form until the call returns.
-struct TopkCall {
-    rs_model* m;
-    explicit TopkCall(rs_model* m_) : m(m_) {}
-    ~TopkCall() { m->topk_k = 0; m->topk_id = nullptr; m->topk_lp = nullptr; }
-    int begin(int k, int32_t* d_top_id, float* d_top_lp) {
-        if (!d_top_id || !d_top_lp) return fail(RS_EARG, "null argument");
-        if (k < 1 || k > RS_TOPK_MAX) return fail(RS_EARG, "k must be 1 .. RS_TOPK_MAX (16)");
-        if (k > m->cfg.vocab) return fail(RS_EARG, "k larger than the vocabulary");
-        if (int r = validate_call(m, MODE_MLM)) return r;
-        HIPTRY(hipSetDevice(m->device));
-        if (m->topk_cand.ensure(topk_cand_bytes(m->vpad)) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(RS_ENOMEM, "top-k candidate workspace (" + std::to_string(topk_cand_bytes(m->vpad)) + " bytes)");
-        }
-        m->topk_k = k; m->topk_id = d_top_id; m->topk_lp = d_top_lp;
-        return RS_OK;
+// A top-k call: checks k and the outputs, makes sure of the candidate workspace and puts the
+// request into the call (head_mlm then runs the top-k decoder form).
+int topk_begin(rs_model* m, int k, int32_t* d_top_id, float* d_top_lp, Call* call) {
+    if (!d_top_id || !d_top_lp) return fail(RS_EARG, "null argument");
+    if (k < 1 || k > RS_TOPK_MAX) return fail(RS_EARG, "k must be 1 .. RS_TOPK_MAX (16)");
+    if (k > m->cfg.vocab) return fail(RS_EARG, "k larger than the vocabulary");
+    if (int r = validate_call(m, MODE_MLM)) return r;
+    TRY_HIP(hipSetDevice(m->device));
+    if (m->topk_cand.ensure(topk_cand_bytes(m->vpad)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(RS_ENOMEM, "top-k candidate workspace (" + std::to_string(topk_cand_bytes(m->vpad)) + " bytes)");
     }
-};
+    call->topk_k = k; call->topk_id = d_top_id; call->topk_lp = d_top_lp;
+    return RS_OK;
+}
 
-// Every entry point that runs the encoder: takes the segment ids left by rs_model_set_token_types
-// (begin: they must cover the call's n_tok tokens) and drops them when the call returns, whatever it
-// returns, so the setting never outlives one call.
-struct TypeCall {
+// Held by every entry point that runs the encoder, from its first line: whatever the entry returns
+// (argument errors and empty calls included), the segment ids left by rs_model_set_token_types are
+// dropped with it, so the setting never outlives one call.  take: they must cover the call's n_tok
+// tokens; the call gets the pointer.
+struct PendingTypes {
     rs_model* m;
-    explicit TypeCall(rs_model* m_) : m(m_) {}
-    ~TypeCall() {
-        if (m) { m->type_next = nullptr; m->type_n = 0; m->type_cur = nullptr; }
+    explicit PendingTypes(rs_model* m_) : m(m_) {}
+    ~PendingTypes() {
+        if (m) { m->type_next = nullptr; m->type_n = 0; }
     }
-    int begin(int64_t n_tok) {
+    int take(int64_t n_tok, Call* call) {
         if (!m->type_next) return RS_OK;
         if (m->type_n != n_tok)
             return fail(RS_EARG, "rs_model_set_token_types gave " + std::to_string(m->type_n) +
                                      " token types, this call addresses " + std::to_string(n_tok) + " tokens");
-        m->type_cur = m->type_next;
+        call->d_type = m->type_next;
         return RS_OK;
     }
 };
+
+// ---- sequence lists of the entry points --------------------------------------------------
+// rs_masked_logprob / rs_masked_topk: the caller's rows (ids already masked) with a query position
+// each; label column 0: the call's device labels replace it, or its log-prob is unused (top-k).
+int rows_query(const int32_t* h_seq_off, const int32_t* h_query, int n_seq, SeqList& sl) {
+    for (int s = 0; s < n_seq; ++s) {
+        const int o = h_seq_off[s], T = h_seq_off[s + 1] - o;
+        if (h_query[s] < 0 || h_query[s] >= T) return fail(RS_EARG, "query position outside its sequence");
+        sl.push(o, T, -1, -1, h_query[s], 0);
+    }
+    return RS_OK;
+}
+// rs_cls_score / token_embed: whole hypotheses with the query at [CLS] (RescoreBert/model.py:19);
+// check(h, o, T): the entry's own test of a hypothesis (its error, or 0).
+template <class Check>
+int rows_whole(const int32_t* h_hyp_off, int n_hyp, SeqList& sl, Check&& check) {
+    for (int h = 0; h < n_hyp; ++h) {
+        const int o = h_hyp_off[h], T = h_hyp_off[h + 1] - o;
+        if (int r = check(h, o, T)) return r;
+        sl.push(o, T, -1, -1, 0, 0);
+    }
+    return RS_OK;
+}
+
+// End of the three PLL entries: the rows' buffer (the caller's, else rowlp_tmp), the run, the
+// float64 sum per hypothesis when d_pll is given, then the finite checks of every output.
+int pll_tail(rs_model* m, hipStream_t st, Call& call, SeqList& sl, const std::vector<int>& hso, int n_hyp,
+             double* d_pll, float* d_row_lp) {
+    float* rows = d_row_lp;
+    if (!rows) {
+        TRY_HIP(m->rowlp_tmp.ensure(std::max<size_t>(sl.size(), 1) * 4));
+        rows = m->rowlp_tmp.as<float>();
+    }
+    int* d_hso = nullptr;
+    call.out_rows = rows; call.extra = &hso; call.d_extra = &d_hso;
+    if (int r = run_all(m, st, call, sl)) return r;
+    if (d_pll) LAUNCH_OTHER(launch_segsum_f64(rows, d_hso, n_hyp, d_pll, st));
+    if (!call.topk_k) return check_finite(m, st, rows, sl.size(), "masked-token log-probability");
+    if (int r = mark_nonfinite(m, st, rows, sl.size())) return r;
+    return check_finite(m, st, call.topk_lp, sl.size() * call.topk_k, "masked-token or top-k log-probability");
+}
+
+// rs_pll_score / rs_pll_topk after their argument checks: every word position of every hypothesis
+// masked in turn (the do_job rows, p = mask_pos); hso: hypothesis -> first sequence.
+int pll_words(rs_model* m, hipStream_t st, PendingTypes& ty, Call& call, const int32_t* h_hyp_off, int n_hyp,
+              double* d_pll, float* d_row_lp) {
+    if (n_hyp == 0) return RS_OK;
+    if (int r = ty.take(h_hyp_off[n_hyp], &call)) return r;
+    CALL_ORDER(m, st);
+    SeqList sl;
+    std::vector<int> hso(n_hyp + 1, 0);
+    for (int h = 0; h < n_hyp; ++h) {
+        const int o = h_hyp_off[h], T = h_hyp_off[h + 1] - o;
+        if (T < 3) return fail(RS_EARG, "hypothesis " + std::to_string(h) + " has no word (T < 3)");
+        for (int p = 1; p <= T - 2; ++p) sl.push(o, T, p, p + 1, p, -1);
+        hso[h + 1] = (int)sl.size();
+    }
+    return pll_tail(m, st, call, sl, hso, n_hyp, d_pll, d_row_lp);
+}
+
+// rs_token_embed, and the first half of rs_bertscore_recall: the L2-normalised last hidden state of
+// every token of the hypotheses into d_emb.  call: MODE_EMB with the caller's tokens and segment ids.
+int token_embed(rs_model* m, hipStream_t st, Call& call, const int32_t* h_hyp_off, int n_hyp, void* d_emb) {
+    SeqList sl;
+    if (int r = rows_whole(h_hyp_off, n_hyp, sl, [](int h, int o, int T) {
+            return o < 0 || T < 1 ? fail(RS_EARG, "hypothesis " + std::to_string(h) + " is empty") : RS_OK;
+        }))
+        return r;
+    call.emb_dst = (f16*)d_emb;
+    if (int r = run_all(m, st, call, sl)) return r;
+    // every token row of the hypotheses (contiguous from h_hyp_off[0]) is written
+    const size_t W = (size_t)m->cfg.hidden * (m->kx == 3 ? 2 : 1);
+    return check_finite(m, st, (const f16*)d_emb + (size_t)h_hyp_off[0] * W,
+                        (size_t)(h_hyp_off[n_hyp] - h_hyp_off[0]) * W, "token embedding");
+}
 
 void prof_collect(rs_model* m) {
     if (m->recs.empty()) return;
@@ -881,14 +930,9 @@ const char* rs_last_error(void) { return g_err.c_str(); }
 int rs_model_create(const rs_bert_cfg* cfg, int device, rs_model** out) {
     if (!cfg || !out) return fail(RS_EARG, "null argument");
     const rs_bert_cfg& c = *cfg;
-    if (c.hidden <= 0 || c.hidden % 256 || c.hidden > 1024) return fail(RS_EUNSUP, "hidden must be 256/512/768/1024");
-    if (c.heads <= 0 || c.hidden / c.heads != 64 || c.hidden % c.heads) return fail(RS_EUNSUP, "head_dim must be 64");
-    if (c.intermediate <= 0 || c.intermediate % 128) return fail(RS_EUNSUP, "intermediate must be a multiple of 128");
-    if (c.layers < 1 || c.vocab < 1 || c.max_pos < 3 || c.type_vocab < 1) return fail(RS_EARG, "bad config");
+    if (int r = check_bert_shape(c, 128)) return r;
     if (!(c.heads_mask & (RS_HEAD_MLM | RS_HEAD_CLS | RS_HEAD_EMB))) return fail(RS_EARG, "heads_mask selects no head");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n)
-        return fail(RS_EHIP, "no such HIP device");
+    if (int r = check_device(device)) return r;
     rs_model* m = new (std::nothrow) rs_model();
     if (!m) return fail(RS_ENOMEM, "alloc");
     m->cfg = c;
@@ -921,7 +965,7 @@ int rs_model_set_tensor(rs_model* m, const char* key, const void* host_ptr, int 
 int rs_model_finalize(rs_model* m) {
     if (!m) return fail(RS_EARG, "null model");
     if (m->finalized) return RS_OK;
-    HIPTRY(hipSetDevice(m->device));
+    TRY_HIP(hipSetDevice(m->device));
     const rs_bert_cfg& c = m->cfg;
     const size_t H = c.hidden, F = c.intermediate, V = c.vocab;
     std::string miss;
@@ -1037,7 +1081,7 @@ int rs_model_finalize(rs_model* m) {
     }
 #undef UP32
 #undef UP16
-    if (!m->call_done) HIPTRY(hipEventCreateWithFlags(&m->call_done, hipEventDisableTiming));
+    if (!m->call_done) TRY_HIP(hipEventCreateWithFlags(&m->call_done, hipEventDisableTiming));
     m->host.clear();
     m->finalized = true;
     return RS_OK;
@@ -1051,35 +1095,16 @@ int rs_model_reserve(rs_model* m, int64_t max_rows) {
 
 int rs_pll_score(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off, int32_t n_hyp,
                  double* d_pll, float* d_row_lp, void* stream) {
-    TypeCall ty(m);
+    PendingTypes ty(m);
     if (!m || !h_hyp_off || n_hyp < 0 || (n_hyp > 0 && (!d_tok || !d_pll))) return fail(RS_EARG, "null argument");
-    hipStream_t st = (hipStream_t)stream;
-    if (n_hyp == 0) return RS_OK;
-    if (int r = ty.begin(h_hyp_off[n_hyp])) return r;
-    CALL_ORDER(m, st);
-    SeqList sl;
-    std::vector<int> hso(n_hyp + 1, 0);
-    for (int h = 0; h < n_hyp; ++h) {
-        const int o = h_hyp_off[h], T = h_hyp_off[h + 1] - o;
-        if (T < 3) return fail(RS_EARG, "hypothesis " + std::to_string(h) + " has no word (T < 3)");
-        for (int p = 1; p <= T - 2; ++p) sl.push(o, T, p, p + 1, p, -1);   // do_job rows, p = mask_pos
-        hso[h + 1] = (int)sl.size();
-    }
-    float* rows = d_row_lp;
-    if (!rows) {
-        HIPTRY(m->rowlp_tmp.ensure(sl.size() * 4));
-        rows = m->rowlp_tmp.as<float>();
-    }
-    int* d_hso = nullptr;
-    if (int r = run_all(m, st, d_tok, sl, MODE_MLM, rows, &hso, &d_hso)) return r;
-    LAUNCH_OTHER(launch_segsum_f64(rows, d_hso, n_hyp, d_pll, st));
-    return check_finite(m, st, rows, sl.size(), "masked-token log-probability");
+    Call call{MODE_MLM, d_tok};
+    return pll_words(m, (hipStream_t)stream, ty, call, h_hyp_off, n_hyp, d_pll, d_row_lp);
 }
 
 int rs_pll_score_spans(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off, int32_t n_hyp,
                        const int32_t* h_row_off, const int32_t* h_lo, const int32_t* h_hi, const int32_t* h_query,
                        double* d_pll, float* d_row_lp, void* stream) {
-    TypeCall ty(m);
+    PendingTypes ty(m);
     if (!m || !h_hyp_off || !h_row_off || n_hyp < 0 || (n_hyp > 0 && (!d_tok || !d_pll)))
         return fail(RS_EARG, "null argument");
     hipStream_t st = (hipStream_t)stream;
@@ -1088,7 +1113,8 @@ int rs_pll_score_spans(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_o
     for (int h = 0; h < n_hyp; ++h)
         if (h_row_off[h + 1] < h_row_off[h]) return fail(RS_EARG, "row_off not ascending at hypothesis " + std::to_string(h));
     if (h_row_off[n_hyp] > 0 && (!h_lo || !h_hi || !h_query)) return fail(RS_EARG, "null argument");
-    if (int r = ty.begin(h_hyp_off[n_hyp])) return r;
+    Call call{MODE_MLM, d_tok};
+    if (int r = ty.take(h_hyp_off[n_hyp], &call)) return r;
     CALL_ORDER(m, st);
     SeqList sl;
     std::vector<int> hso(h_row_off, h_row_off + n_hyp + 1);     // one sequence per row
@@ -1103,130 +1129,84 @@ int rs_pll_score_spans(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_o
             sl.push(o, T, h_lo[r], h_hi[r], h_query[r], -1);
         }
     }
-    float* rows = d_row_lp;
-    if (!rows) {
-        HIPTRY(m->rowlp_tmp.ensure(std::max<size_t>(sl.size(), 1) * 4));
-        rows = m->rowlp_tmp.as<float>();
-    }
-    int* d_hso = nullptr;
-    if (int r = run_all(m, st, d_tok, sl, MODE_MLM, rows, &hso, &d_hso)) return r;
-    LAUNCH_OTHER(launch_segsum_f64(rows, d_hso, n_hyp, d_pll, st));
-    return check_finite(m, st, rows, sl.size(), "masked-token log-probability");
+    return pll_tail(m, st, call, sl, hso, n_hyp, d_pll, d_row_lp);
 }
 
 int rs_masked_logprob(rs_model* m, const int32_t* d_ids, const int32_t* h_seq_off,
                       const int32_t* h_query, const int32_t* d_label, int32_t n_seq, float* d_out,
                       void* stream) {
-    TypeCall ty(m);
+    PendingTypes ty(m);
     if (!m || !h_seq_off || !h_query || n_seq < 0 || (n_seq > 0 && (!d_ids || !d_label || !d_out)))
         return fail(RS_EARG, "null argument");
     if (n_seq == 0) return RS_OK;
-    if (int r = ty.begin(h_seq_off[n_seq])) return r;
-    CALL_ORDER(m, (hipStream_t)stream);
+    Call call{MODE_MLM, d_ids, d_out, d_label};
+    if (int r = ty.take(h_seq_off[n_seq], &call)) return r;
+    hipStream_t st = (hipStream_t)stream;
+    CALL_ORDER(m, st);
     SeqList sl;
-    for (int s = 0; s < n_seq; ++s) {
-        const int o = h_seq_off[s], T = h_seq_off[s + 1] - o;
-        if (h_query[s] < 0 || h_query[s] >= T) return fail(RS_EARG, "query position outside its sequence");
-        sl.push(o, T, -1, -1, h_query[s], 0);   // ids already masked by the caller
-    }
-    if (int r = run_all(m, (hipStream_t)stream, d_ids, sl, MODE_MLM, d_out, nullptr, nullptr, d_label)) return r;
-    return check_finite(m, (hipStream_t)stream, d_out, (size_t)n_seq, "masked-token log-probability");
+    if (int r = rows_query(h_seq_off, h_query, n_seq, sl)) return r;
+    if (int r = run_all(m, st, call, sl)) return r;
+    return check_finite(m, st, d_out, (size_t)n_seq, "masked-token log-probability");
 }
 
 int rs_masked_topk(rs_model* m, const int32_t* d_ids, const int32_t* h_seq_off, const int32_t* h_query,
                    int32_t n_seq, int32_t k, int32_t* d_top_id, float* d_top_lp, void* stream) {
-    TypeCall ty(m);
+    PendingTypes ty(m);
     if (!m || !h_seq_off || !h_query || n_seq < 0 || (n_seq > 0 && !d_ids)) return fail(RS_EARG, "null argument");
-    TopkCall tk(m);
-    if (int r = tk.begin(k, d_top_id, d_top_lp)) return r;
+    Call call{MODE_MLM, d_ids};
+    if (int r = topk_begin(m, k, d_top_id, d_top_lp, &call)) return r;
     if (n_seq == 0) return RS_OK;
-    if (int r = ty.begin(h_seq_off[n_seq])) return r;
+    if (int r = ty.take(h_seq_off[n_seq], &call)) return r;
     hipStream_t st = (hipStream_t)stream;
     CALL_ORDER(m, st);
     SeqList sl;
-    for (int s = 0; s < n_seq; ++s) {
-        const int o = h_seq_off[s], T = h_seq_off[s + 1] - o;
-        if (h_query[s] < 0 || h_query[s] >= T) return fail(RS_EARG, "query position outside its sequence");
-        sl.push(o, T, -1, -1, h_query[s], 0);   // ids already masked by the caller; label column 0, its log-prob unused
-    }
-    HIPTRY(m->rowlp_tmp.ensure(sl.size() * 4));
-    if (int r = run_all(m, st, d_ids, sl, MODE_MLM, m->rowlp_tmp.as<float>(), nullptr, nullptr)) return r;
+    if (int r = rows_query(h_seq_off, h_query, n_seq, sl)) return r;
+    TRY_HIP(m->rowlp_tmp.ensure(sl.size() * 4));
+    call.out_rows = m->rowlp_tmp.as<float>();
+    if (int r = run_all(m, st, call, sl)) return r;
     return check_finite(m, st, d_top_lp, (size_t)n_seq * k, "top-k log-probability");
 }
 
 int rs_pll_topk(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off, int32_t n_hyp, int32_t k,
                 double* d_pll, float* d_row_lp, int32_t* d_top_id, float* d_top_lp, void* stream) {
-    TypeCall ty(m);
+    PendingTypes ty(m);
     if (!m || !h_hyp_off || n_hyp < 0 || (n_hyp > 0 && !d_tok)) return fail(RS_EARG, "null argument");
-    TopkCall tk(m);
-    if (int r = tk.begin(k, d_top_id, d_top_lp)) return r;
-    if (n_hyp == 0) return RS_OK;
-    if (int r = ty.begin(h_hyp_off[n_hyp])) return r;
-    hipStream_t st = (hipStream_t)stream;
-    CALL_ORDER(m, st);
-    SeqList sl;
-    std::vector<int> hso(n_hyp + 1, 0);
-    for (int h = 0; h < n_hyp; ++h) {
-        const int o = h_hyp_off[h], T = h_hyp_off[h + 1] - o;
-        if (T < 3) return fail(RS_EARG, "hypothesis " + std::to_string(h) + " has no word (T < 3)");
-        for (int p = 1; p <= T - 2; ++p) sl.push(o, T, p, p + 1, p, -1);   // the rows of rs_pll_score
-        hso[h + 1] = (int)sl.size();
-    }
-    float* rows = d_row_lp;
-    if (!rows) {
-        HIPTRY(m->rowlp_tmp.ensure(sl.size() * 4));
-        rows = m->rowlp_tmp.as<float>();
-    }
-    int* d_hso = nullptr;
-    if (int r = run_all(m, st, d_tok, sl, MODE_MLM, rows, &hso, &d_hso)) return r;
-    if (d_pll) LAUNCH_OTHER(launch_segsum_f64(rows, d_hso, n_hyp, d_pll, st));
-    if (int r = mark_nonfinite(m, st, rows, sl.size())) return r;
-    return check_finite(m, st, d_top_lp, sl.size() * k, "masked-token or top-k log-probability");
+    Call call{MODE_MLM, d_tok};
+    if (int r = topk_begin(m, k, d_top_id, d_top_lp, &call)) return r;
+    return pll_words(m, (hipStream_t)stream, ty, call, h_hyp_off, n_hyp, d_pll, d_row_lp);
 }
 
 int rs_cls_score(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off, int32_t n_hyp,
                  float* d_out, void* stream) {
-    TypeCall ty(m);
+    PendingTypes ty(m);
     if (!m || !h_hyp_off || n_hyp < 0 || (n_hyp > 0 && (!d_tok || !d_out))) return fail(RS_EARG, "null argument");
     if (n_hyp == 0) return RS_OK;
-    if (int r = ty.begin(h_hyp_off[n_hyp])) return r;
-    CALL_ORDER(m, (hipStream_t)stream);
+    Call call{MODE_CLS, d_tok, d_out};
+    if (int r = ty.take(h_hyp_off[n_hyp], &call)) return r;
+    hipStream_t st = (hipStream_t)stream;
+    CALL_ORDER(m, st);
     SeqList sl;
-    for (int h = 0; h < n_hyp; ++h) {
-        const int o = h_hyp_off[h], T = h_hyp_off[h + 1] - o;
-        if (T < 1) return fail(RS_EARG, "empty hypothesis");
-        sl.push(o, T, -1, -1, 0, 0);      // query = [CLS] (RescoreBert/model.py:19)
-    }
-    if (int r = run_all(m, (hipStream_t)stream, d_tok, sl, MODE_CLS, d_out, nullptr, nullptr)) return r;
-    return check_finite(m, (hipStream_t)stream, d_out, (size_t)n_hyp, "RescoreBert score");
+    if (int r = rows_whole(h_hyp_off, n_hyp, sl,
+                           [](int, int, int T) { return T < 1 ? fail(RS_EARG, "empty hypothesis") : RS_OK; }))
+        return r;
+    if (int r = run_all(m, st, call, sl)) return r;
+    return check_finite(m, st, d_out, (size_t)n_hyp, "RescoreBert score");
 }
 
 int rs_token_embed(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off, int32_t n_hyp,
                    void* d_emb, void* stream) {
-    TypeCall ty(m);
+    PendingTypes ty(m);
     if (!m || !h_hyp_off || n_hyp < 0 || (n_hyp > 0 && (!d_tok || !d_emb))) return fail(RS_EARG, "null argument");
     if (n_hyp == 0) return RS_OK;
-    if (int r = ty.begin(h_hyp_off[n_hyp])) return r;
+    Call call{MODE_EMB, d_tok};
+    if (int r = ty.take(h_hyp_off[n_hyp], &call)) return r;
     CALL_ORDER(m, (hipStream_t)stream);
-    SeqList sl;
-    for (int h = 0; h < n_hyp; ++h) {
-        const int o = h_hyp_off[h], T = h_hyp_off[h + 1] - o;
-        if (o < 0 || T < 1) return fail(RS_EARG, "hypothesis " + std::to_string(h) + " is empty");
-        sl.push(o, T, -1, -1, 0, 0);
-    }
-    m->emb_dst = (f16*)d_emb;
-    const int r = run_all(m, (hipStream_t)stream, d_tok, sl, MODE_EMB, nullptr, nullptr, nullptr);
-    m->emb_dst = nullptr;
-    if (r) return r;
-    // every token row of the hypotheses (contiguous from h_hyp_off[0]) is written
-    const size_t W = (size_t)m->cfg.hidden * (m->kx == 3 ? 2 : 1);
-    return check_finite(m, (hipStream_t)stream, (const f16*)d_emb + (size_t)h_hyp_off[0] * W,
-                        (size_t)(h_hyp_off[n_hyp] - h_hyp_off[0]) * W, "token embedding");
+    return token_embed(m, (hipStream_t)stream, call, h_hyp_off, n_hyp, d_emb);
 }
 
 int rs_bertscore_recall(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off,
                         const int32_t* h_utt_off, int32_t n_utt, float* d_rmat, float* d_rmat0, void* stream) {
-    TypeCall ty(m);          // (the ids are taken by the rs_token_embed call below)
+    PendingTypes ty(m);
     if (!m || !h_hyp_off || !h_utt_off || n_utt < 0 || (n_utt > 0 && (!d_tok || !d_rmat)))
         return fail(RS_EARG, "null argument");
     if (n_utt == 0) return RS_OK;
@@ -1244,8 +1224,12 @@ int rs_bertscore_recall(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_
     const size_t n_tok = (size_t)h_hyp_off[n_hyp];
     const bool two = m->kx == 3;                 // fp16x3: two-part embeddings, split-operand cosines
     const int COLS = bertscore_cols(two);
-    HIPTRY(m->emb.ensure(std::max<size_t>(n_tok, 1) * H * 2 * (two ? 2 : 1)));
-    if (int r = rs_token_embed(m, d_tok, h_hyp_off, n_hyp, m->emb.p, stream)) return r;
+    TRY_HIP(m->emb.ensure(std::max<size_t>(n_tok, 1) * H * 2 * (two ? 2 : 1)));
+    if (n_hyp > 0) {
+        Call call{MODE_EMB, d_tok};
+        if (int r = ty.take(h_hyp_off[n_hyp], &call)) return r;
+        if (int r = token_embed(m, st, call, h_hyp_off, n_hyp, m->emb.p)) return r;
+    }
     // plan: runs of whole ref hypotheses fitting one COLS-column tile (a longer one alone)
     std::vector<int> items;
     std::vector<long long> moff(n_utt + 1, 0);
@@ -1266,13 +1250,13 @@ int rs_bertscore_recall(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_
     // one upload: items | mat_off (int64) | hyp_off | utt_off
     const size_t w_items = items.size(), w_moff = 2 * (size_t)(n_utt + 1);
     const size_t n_int = w_items + w_moff + (size_t)(n_hyp + 1) + (size_t)(n_utt + 1);
-    HIPTRY(m->stage_plan.begin(n_int));
+    TRY_HIP(m->stage_plan.begin(n_int));
     int* p = m->stage_plan.p;
     std::memcpy(p, items.data(), w_items * 4);
     std::memcpy(p + w_items, moff.data(), w_moff * 4);
     std::memcpy(p + w_items + w_moff, h_hyp_off, (size_t)(n_hyp + 1) * 4);
     std::memcpy(p + w_items + w_moff + n_hyp + 1, h_utt_off, (size_t)(n_utt + 1) * 4);
-    HIPTRY(m->stage_plan.upload(m->plan, n_int, st));
+    TRY_HIP(m->stage_plan.upload(m->plan, n_int, st));
     int* d = m->plan.as<int>();
     LAUNCH_OTHER(launch_bertscore_recall(m->emb.as<f16>(), H, d + w_items + w_moff, d + w_items + w_moff + n_hyp + 1,
                                          (const long long*)(d + w_items), (const int4*)d, n_items, d_rmat, d_rmat0, st,

@@ -25,53 +25,18 @@
 
 #include "common.h"
 #include "train.h"
-
-int rs_fail(int code, const std::string& msg);
+#include "host_util.h"
 
 namespace {
 
-#define TRY_HIP(expr)                                                                       \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess) return rs_fail(RS_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-// allocations: out of memory comes back as RS_ENOMEM (the saved attention probabilities of long
-// batches are the large one: layers * sum_s heads * T_s^2 * 4 bytes)
-#define TRY_ALLOC(expr)                                                                     \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ == hipErrorOutOfMemory) {                                                    \
-            (void)hipGetLastError();                                                        \
-            return rs_fail(RS_ENOMEM, std::string(#expr) + ": out of device memory");       \
-        }                                                                                   \
-        if (e_ != hipSuccess) return rs_fail(RS_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
+// (TRY_ALLOC: the saved attention probabilities of long batches are the large allocation,
+// layers * sum_s heads * T_s^2 * 4 bytes)
 #define TRY_BLAS(expr)                                                                      \
     do {                                                                                    \
         rocblas_status s_ = (expr);                                                         \
         if (s_ != rocblas_status_success)                                                   \
             return rs_fail(RS_EHIP, std::string(#expr) + ": " + rocblas_status_to_string(s_)); \
     } while (0)
-
-struct Buf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    hipError_t ensure(size_t n) {
-        if (n <= bytes) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-        hipError_t e = hipMalloc(&p, n);
-        if (e == hipSuccess) bytes = n;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
-    float* f() const { return (float*)p; }
-};
 
 struct TLayer {
     size_t wqkv, bqkv, wo, bo, g1, be1, w1, b1, w2, b2, g2, be2;
@@ -93,8 +58,8 @@ struct rs_trainer {
     size_t o_word = 0, o_pos = 0, o_type = 0, o_eg = 0, o_eb = 0, o_wl = 0, o_bl = 0;
     size_t o_wt = 0, o_bt = 0, o_tg = 0, o_tb = 0, o_db = 0;   // MLM head (decoder tied to o_word)
     std::vector<TLayer> lay;
-    Buf P, G, M1, V1;       // parameters, gradients, Adam moments
-    Buf act, grad, meta, small, ws;   // ws: split-K partials of tr_sgemm
+    DevBuf P, G, M1, V1;       // parameters, gradients, Adam moments
+    DevBuf act, grad, meta, small, ws;   // ws: split-K partials of tr_sgemm
     long long step = 0;
     uint64_t drop_step = 0;         // dropout-step counter (key of the next dropout-active step)
     std::vector<int> h_tok, h_meta, h_type;
@@ -126,12 +91,6 @@ rocblas_status blas_tn(rocblas_handle h, int M, int N, int K, const float* dY, c
     return rocblas_sgemm(h, rocblas_operation_none, rocblas_operation_transpose, K, N, M, &one, X, K, dY, N, &beta, dW, K);
 }
 
-#define TRY_SG(expr)                                                                        \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess) return rs_fail(RS_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 #define RS_TRY(expr)                     \
     do {                                 \
         if (int r_ = (expr)) return r_;  \
@@ -143,7 +102,7 @@ int gemm_nt(rs_trainer* t, hipStream_t st, int M, int N, int K, const float* X, 
         TRY_BLAS(blas_nt(t->blas, M, N, K, X, W, Y, beta));
         return RS_OK;
     }
-    TRY_SG(tr_sgemm(M, N, K, X, K, true, W, K, true, Y, N, beta != 0.f, t->ws.f(), t->ws.bytes / 4, st));
+    TRY_HIP(tr_sgemm(M, N, K, X, K, true, W, K, true, Y, N, beta != 0.f, t->ws.as<float>(), t->ws.bytes / 4, st));
     return RS_OK;
 }
 // row-major dX[M, K] = dY[M, N] . W[N, K] (+ beta dX)
@@ -152,7 +111,7 @@ int gemm_nn(rs_trainer* t, hipStream_t st, int M, int N, int K, const float* dY,
         TRY_BLAS(blas_nn(t->blas, M, N, K, dY, W, dX, beta));
         return RS_OK;
     }
-    TRY_SG(tr_sgemm(M, K, N, dY, N, true, W, K, false, dX, K, beta != 0.f, t->ws.f(), t->ws.bytes / 4, st));
+    TRY_HIP(tr_sgemm(M, K, N, dY, N, true, W, K, false, dX, K, beta != 0.f, t->ws.as<float>(), t->ws.bytes / 4, st));
     return RS_OK;
 }
 // row-major dW[N, K] = dY[M, N]^T . X[M, K] (+ beta dW)
@@ -161,7 +120,7 @@ int gemm_tn(rs_trainer* t, hipStream_t st, int M, int N, int K, const float* dY,
         TRY_BLAS(blas_tn(t->blas, M, N, K, dY, X, dW, beta));
         return RS_OK;
     }
-    TRY_SG(tr_sgemm(N, K, M, dY, N, false, X, K, false, dW, K, beta != 0.f, t->ws.f(), t->ws.bytes / 4, st));
+    TRY_HIP(tr_sgemm(N, K, M, dY, N, false, X, K, false, dW, K, beta != 0.f, t->ws.as<float>(), t->ws.bytes / 4, st));
     return RS_OK;
 }
 
@@ -186,15 +145,11 @@ extern "C" {
 int rs_trainer_create(const rs_bert_cfg* cfg, int device, rs_trainer** out) {
     if (!cfg || !out) return rs_fail(RS_EARG, "null argument");
     const rs_bert_cfg& c = *cfg;
-    if (c.hidden <= 0 || c.hidden % 256 || c.hidden > 1024) return rs_fail(RS_EUNSUP, "hidden must be 256/512/768/1024");
-    if (c.heads <= 0 || c.hidden / c.heads != 64 || c.hidden % c.heads) return rs_fail(RS_EUNSUP, "head_dim must be 64");
-    if (c.intermediate <= 0 || c.intermediate % 4) return rs_fail(RS_EUNSUP, "intermediate must be a multiple of 4");
-    if (c.layers < 1 || c.vocab < 1 || c.max_pos < 3 || c.type_vocab < 1) return rs_fail(RS_EARG, "bad config");
+    if (int r = check_bert_shape(c, 4)) return r;
     if (c.heads_mask != RS_HEAD_CLS && c.heads_mask != RS_HEAD_MLM)
         return rs_fail(RS_EUNSUP, "the trainer takes one head: RS_HEAD_CLS (RescoreBert) or RS_HEAD_MLM (MLM fine-tuning)");
     if (c.heads_mask == RS_HEAD_MLM && c.vocab % 4) return rs_fail(RS_EUNSUP, "MLM training needs vocab % 4 == 0");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return rs_fail(RS_EHIP, "no such HIP device");
+    if (int r = check_device(device)) return r;
     int attn_mode = 0;
     if (const char* v = getenv("RS_TRAIN_ATTN")) {
         const std::string m(v);
@@ -301,7 +256,7 @@ int rs_trainer_finalize(rs_trainer* t) {
     return RS_OK;
 }
 
-static int copy_out(rs_trainer* t, const Buf& b, const char* key, void* host_out, int64_t numel) {
+static int copy_out(rs_trainer* t, const DevBuf& b, const char* key, void* host_out, int64_t numel) {
     if (!t || !key || !host_out) return rs_fail(RS_EARG, "null argument");
     if (!t->finalized) return rs_fail(RS_ESTATE, "rs_trainer_finalize not called");
     auto it = t->table.find(key);
@@ -309,16 +264,16 @@ static int copy_out(rs_trainer* t, const Buf& b, const char* key, void* host_out
     if ((size_t)numel != it->second.second) return rs_fail(RS_EARG, std::string("tensor ") + key + " has a different size");
     TRY_HIP(hipSetDevice(t->device));
     TRY_HIP(hipDeviceSynchronize());
-    TRY_HIP(hipMemcpy(host_out, b.f() + it->second.first, (size_t)numel * 4, hipMemcpyDeviceToHost));
+    TRY_HIP(hipMemcpy(host_out, b.as<float>() + it->second.first, (size_t)numel * 4, hipMemcpyDeviceToHost));
     return RS_OK;
 }
 
 int rs_trainer_get_tensor(rs_trainer* t, const char* key, void* host_out, int64_t numel) {
-    return copy_out(t, t ? t->P : Buf{}, key, host_out, numel);
+    return copy_out(t, t ? t->P : DevBuf{}, key, host_out, numel);
 }
 
 int rs_trainer_get_grad(rs_trainer* t, const char* key, void* host_out, int64_t numel) {
-    return copy_out(t, t ? t->G : Buf{}, key, host_out, numel);
+    return copy_out(t, t ? t->G : DevBuf{}, key, host_out, numel);
 }
 
 }  // extern "C"
@@ -363,7 +318,7 @@ struct StepCtx {
 };
 
 // A training step takes the segment ids left by rs_trainer_set_token_types and drops the setting
-// when it returns, whatever it returns (the scorer's TypeCall).
+// when it returns, whatever it returns (the scorer's PendingTypes).
 struct TypeStep {
     rs_trainer* t;
     const int32_t* d_type = nullptr;
@@ -503,7 +458,7 @@ int prepare(StepCtx& c, const TypeStep& ty, const int32_t* d_tok, const int32_t*
     const size_t n_grad = 2 * MH + QKV + MF + n_part + n_tail + (c.tiled ? PS : 0);
     TRY_ALLOC(t->grad.ensure(n_grad * 4));
     TRY_ALLOC(t->ws.ensure(std::max<size_t>(sgemm_ws_floats(cf, M), 64) * 4));
-    float* A = t->act.f();
+    float* A = t->act.as<float>();
     c.x0 = A;
     c.st0 = (float2*)(c.x0 + MH);
     float* lbase = c.x0 + MH + M2;
@@ -531,7 +486,7 @@ int prepare(StepCtx& c, const TypeStep& ty, const int32_t* d_tok, const int32_t*
         c.tst = (float2*)(c.th + MH);
         c.logits = c.th + MH + M2;
     }
-    float* G = t->grad.f();
+    float* G = t->grad.as<float>();
     c.dA = G;
     c.dB = c.dA + MH;
     c.dQKV = c.dB + MH;
@@ -546,7 +501,7 @@ int encoder_forward(StepCtx& c) {
     rs_trainer* t = c.t;
     const rs_bert_cfg& cf = t->cfg;
     const int H = cf.hidden, F = cf.intermediate, nh = cf.heads, M = c.M;
-    float* Pm = t->P.f();
+    float* Pm = t->P.as<float>();
     hipStream_t st = c.st;
     TRY_HIP(tr_embed_ln(c.dm + c.i_tok, c.dm + c.i_pos, c.row_type(), M, cf.vocab, cf.type_vocab, Pm + t->o_word,
                         Pm + t->o_pos, Pm + t->o_type, Pm + t->o_eg, Pm + t->o_eb, cf.ln_eps, H, c.x0, c.st0, c.la[0].hin,
@@ -582,7 +537,7 @@ int encoder_backward(StepCtx& c) {
     const rs_bert_cfg& cf = t->cfg;
     const int H = cf.hidden, F = cf.intermediate, nh = cf.heads, M = c.M;
     const size_t MH = (size_t)M * H, MF = (size_t)M * F;
-    float *Pm = t->P.f(), *Gm = t->G.f();
+    float *Pm = t->P.as<float>(), *Gm = t->G.as<float>();
     float *dA = c.dA, *dB = c.dB, *dF = c.dF, *dQKV = c.dQKV, *part = c.part;
     hipStream_t st = c.st;
     for (int l = cf.layers - 1; l >= 0; --l) {
@@ -650,8 +605,8 @@ int adamw(rs_trainer* t, const rs_train_opts* o, hipStream_t st) {
     const double bc2 = 1.0 - std::pow((double)o->beta2, (double)t->step);
     // python-float (double) scalars as torch computes them, cast to the fp32 tensor dtype
     const float decay = (float)(1.0 - (double)o->lr * (double)o->weight_decay);
-    TRY_HIP(tr_adamw(t->P.f(), t->G.f(), t->M1.f(), t->V1.f(), (long long)t->n_params, decay,
-                     (float)(1.0 - (double)o->beta1), o->beta2, (float)(1.0 - (double)o->beta2),
+    TRY_HIP(tr_adamw(t->P.as<float>(), t->G.as<float>(), t->M1.as<float>(), t->V1.as<float>(), (long long)t->n_params,
+                     decay, (float)(1.0 - (double)o->beta1), o->beta2, (float)(1.0 - (double)o->beta2),
                      (float)((double)o->lr / bc1), (float)std::sqrt(bc2), o->eps, st));
     return RS_OK;
 }
@@ -680,7 +635,7 @@ int rs_train_step_cls(rs_trainer* t, const int32_t* d_tok, const int32_t* h_hyp_
     if (int r = prepare(c, ty, d_tok, h_hyp_off, n_hyp, std::vector<int>(h_utt_off, h_utt_off + n_utt + 1))) return r;
     if (int r = encoder_forward(c)) return r;
     const int H = t->cfg.hidden, S = c.S;
-    float *Pm = t->P.f(), *Gm = t->G.f();
+    float *Pm = t->P.as<float>(), *Gm = t->G.as<float>();
     float* sc = c.tail;
     float* dsc = sc + S;
     float* uloss = dsc + S;
@@ -720,7 +675,7 @@ int rs_train_step_mlm(rs_trainer* t, const int32_t* d_ids, const int32_t* h_seq_
     if (int r = encoder_forward(c)) return r;
     const rs_bert_cfg& cf = t->cfg;
     const int H = cf.hidden, V = cf.vocab, M = c.M;
-    float *Pm = t->P.f(), *Gm = t->G.f();
+    float *Pm = t->P.as<float>(), *Gm = t->G.as<float>();
     hipStream_t st = c.st;
     const float* hfin = c.la[cf.layers].hin;
     // BertOnlyMLMHead: transform (dense + GELU + LN), tied decoder + bias (modeling_bert.py:466-506)
@@ -799,7 +754,7 @@ void rs_trainer_destroy(rs_trainer* t) {
     (void)hipSetDevice(t->device);
     (void)hipDeviceSynchronize();
     if (t->blas) (void)rocblas_destroy_handle(t->blas);
-    for (Buf* b : {&t->P, &t->G, &t->M1, &t->V1, &t->act, &t->grad, &t->meta, &t->small, &t->ws}) b->release();
+    for (DevBuf* b : {&t->P, &t->G, &t->M1, &t->V1, &t->act, &t->grad, &t->meta, &t->small, &t->ws}) b->release();
     delete t;
 }
 

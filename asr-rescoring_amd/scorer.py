@@ -53,18 +53,13 @@ class BertEngine:
         self.device = torch.device("cuda", torch.device(device).index if not isinstance(device, int)
                                    else device)
         torch.cuda.set_device(self.device)
-        cfg = _lib.RsBertCfg(shape.vocab, shape.hidden, shape.layers, shape.heads, shape.intermediate,
-                             shape.max_pos, shape.type_vocab, shape.ln_eps, shape.mask_id, heads,
-                             _lib.RS_PREC[precision])
+        cfg = _lib.bert_cfg(shape, heads, precision)
         self.precision = precision
         h = ctypes.c_void_p()
         _lib.check(self.lib.rs_model_create(ctypes.byref(cfg), self.device.index, ctypes.byref(h)))
         self.handle = h
         try:
-            for k, v in weights.items():
-                a = np.ascontiguousarray(v, dtype=np.float32)
-                shp = (ctypes.c_int64 * a.ndim)(*a.shape)
-                _lib.check(self.lib.rs_model_set_tensor(self.handle, k.encode(), a.ctypes.data, 0, shp, a.ndim))
+            _lib.upload_tensors(self.lib.rs_model_set_tensor, self.handle, weights)
             _lib.check(self.lib.rs_model_finalize(self.handle))
             _lib.check(self.lib.rs_model_reserve(self.handle, int(max_rows)))
         except Exception:
@@ -111,6 +106,11 @@ class BertEngine:
             return tokens.to(self.device, torch.int32).contiguous()
         return torch.from_numpy(np.ascontiguousarray(tokens, np.int32)).to(self.device)
 
+    def _hyps(self, tokens, hyp_off):
+        """A ragged hypothesis list as the C ABI takes it: (device tokens, int32 offsets, count)."""
+        off = np.ascontiguousarray(hyp_off, np.int32)
+        return self._dev_tokens(tokens), off, len(off) - 1
+
     # ---- segment ids (rs_model_set_token_types) ----------------------------------------
     def _set_types(self, token_types):
         """Hands ``token_types`` (one segment id per token of the NEXT scoring call, array or tensor;
@@ -133,14 +133,26 @@ class BertEngine:
         _lib.check(self.lib.rs_model_set_token_types(self.handle, None, 0))
 
 
-def _padded_types(token_type_ids, keep: torch.Tensor):
-    """Ragged copy of a padded [B, T] ``token_type_ids`` batch, gathered like ``input_ids``."""
-    if token_type_ids is None:
-        return None
-    tt = token_type_ids.to(keep.device)
-    if tt.shape != keep.shape:
-        raise ValueError("token_type_ids must have the shape of input_ids")
-    return tt[keep].to(torch.int32).contiguous()
+def _ragged(input_ids: torch.Tensor, attention_mask: torch.Tensor, token_type_ids, device):
+    """Ragged copy of a right-padded [B, T] batch, the unpadded prefix of each row (device gather,
+    no host round trip): (ids int32 [sum len], row offsets int32 [B + 1], types like ids or None)."""
+    lens = _prefix_lengths(attention_mask)
+    ids = input_ids.to(device)
+    keep = torch.arange(ids.shape[1], device=device)[None, :] < torch.from_numpy(lens).to(device)[:, None]
+    off = np.zeros(len(lens) + 1, np.int32)
+    off[1:] = np.cumsum(lens)
+    types = None
+    if token_type_ids is not None:
+        types = token_type_ids.to(device)
+        if types.shape != keep.shape:
+            raise ValueError("token_type_ids must have the shape of input_ids")
+        types = types[keep].to(torch.int32).contiguous()
+    return ids[keep].to(torch.int32).contiguous(), off, types
+
+
+def _word_rows(off: np.ndarray) -> int:
+    """Masked rows of ``rs_pll_score`` / ``rs_pll_topk``: one per word position ([CLS] w.. [SEP])."""
+    return int((np.diff(off) - 2).sum()) if len(off) > 1 else 0
 
 
 class PLLScorer(BertEngine):
@@ -172,12 +184,9 @@ class PLLScorer(BertEngine):
                 raise ValueError(f"variant {variant!r} needs word_start")
             return self.score_spans(tokens, hyp_off, *pll_spans(hyp_off, word_start, variant, score_from=score_from),
                                     return_rows=return_rows, token_types=token_types)
-        off = np.ascontiguousarray(hyp_off, np.int32)
-        n_hyp = len(off) - 1
-        d_tok = self._dev_tokens(tokens)
-        n_rows = int((np.diff(off) - 2).sum()) if n_hyp else 0
+        d_tok, off, n_hyp = self._hyps(tokens, hyp_off)
         pll = torch.empty(n_hyp, dtype=torch.float64, device=self.device)
-        rows = torch.empty(n_rows, dtype=torch.float32, device=self.device) if return_rows else None
+        rows = torch.empty(_word_rows(off), dtype=torch.float32, device=self.device) if return_rows else None
         d_type = self._set_types(token_types)      # noqa: F841  (alive until the call has returned)
         _lib.check(self.lib.rs_pll_score(self.handle, _lib.ptr(d_tok), off.ctypes.data, n_hyp,
                                          _lib.ptr(pll), _lib.ptr(rows), _lib.stream_ptr(self.device)))
@@ -192,8 +201,7 @@ class PLLScorer(BertEngine):
 
         Returns float64 [H] device tensor (sum of each hypothesis' rows in row order; no rows: 0)
         and, with ``return_rows``, the float32 per-row log-probs."""
-        off = np.ascontiguousarray(hyp_off, np.int32)
-        n_hyp = len(off) - 1
+        d_tok, off, n_hyp = self._hyps(tokens, hyp_off)
         roff = np.ascontiguousarray(row_off, np.int32)
         if len(roff) != n_hyp + 1:
             raise ValueError("row_off must have one entry per hypothesis plus one")
@@ -201,7 +209,6 @@ class PLLScorer(BertEngine):
         cols = [None if c is None else np.ascontiguousarray(c, np.int32) for c in (lo, hi, query)]
         if any(c is not None and len(c) != n_rows for c in cols):
             raise ValueError("lo, hi and query must have row_off[-1] entries")
-        d_tok = self._dev_tokens(tokens)
         pll = torch.empty(n_hyp, dtype=torch.float64, device=self.device)
         rows = torch.empty(n_rows, dtype=torch.float32, device=self.device) if return_rows else None
         d_type = self._set_types(token_types)      # noqa: F841
@@ -220,23 +227,20 @@ class PLLScorer(BertEngine):
 
         ``attention_mask`` rows must be a prefix of ones (``pad_sequence`` output);
         ``token_type_ids``: padded [B, T] segment ids as transformers takes them."""
-        lens = _prefix_lengths(attention_mask)
+        d_ids, off, types = _ragged(input_ids, attention_mask, token_type_ids, self.device)
         B = input_ids.shape[0]
         mp = np.asarray([int(x) for x in mask_pos], np.int32)
-        ids = input_ids.to(self.device)
-        # ragged copy of the unpadded prefix of each row (device gather, no host round trip)
-        T = ids.shape[1]
-        keep = (torch.arange(T, device=self.device)[None, :] < torch.from_numpy(lens).to(self.device)[:, None])
-        d_ids = ids[keep].to(torch.int32).contiguous()
-        off = np.zeros(B + 1, np.int32)
-        off[1:] = np.cumsum(lens)
         lab = labels.to(self.device)[torch.arange(B, device=self.device),
                                      torch.from_numpy(mp.astype(np.int64)).to(self.device)]
-        lab = lab.to(torch.int32).contiguous()
-        out = torch.empty(B, dtype=torch.float32, device=self.device)
-        d_type = self._set_types(_padded_types(token_type_ids, keep))      # noqa: F841
-        _lib.check(self.lib.rs_masked_logprob(self.handle, _lib.ptr(d_ids), off.ctypes.data,
-                                              mp.ctypes.data, _lib.ptr(lab), B, _lib.ptr(out),
+        return self._masked_logprob(d_ids, off, mp, lab.to(torch.int32).contiguous(), types)
+
+    def _masked_logprob(self, d_ids, off, mp, lab, token_types=None) -> torch.Tensor:
+        """``rs_masked_logprob`` on ragged rows (device ids and labels, int32 offsets and query
+        positions): float32 [R] device tensor."""
+        out = torch.empty(len(off) - 1, dtype=torch.float32, device=self.device)
+        d_type = self._set_types(token_types)      # noqa: F841
+        _lib.check(self.lib.rs_masked_logprob(self.handle, _lib.ptr(d_ids), off.ctypes.data, mp.ctypes.data,
+                                              _lib.ptr(lab), len(off) - 1, _lib.ptr(out),
                                               _lib.stream_ptr(self.device)))
         return out
 
@@ -247,18 +251,12 @@ class PLLScorer(BertEngine):
         of MLM_PLL/main.py:101-105 without the [B, vocab] rows.  Returns device tensors
         (ids int32 [B, k], logprob float32 [B, k]), best first, equal logits by the lower id.
         ``token_type_ids``: padded [B, T] segment ids."""
-        lens = _prefix_lengths(attention_mask)
+        d_ids, off, types = _ragged(input_ids, attention_mask, token_type_ids, self.device)
         B = input_ids.shape[0]
         mp = np.asarray([int(x) for x in mask_pos], np.int32)
-        ids = input_ids.to(self.device)
-        T = ids.shape[1]
-        keep = (torch.arange(T, device=self.device)[None, :] < torch.from_numpy(lens).to(self.device)[:, None])
-        d_ids = ids[keep].to(torch.int32).contiguous()
-        off = np.zeros(B + 1, np.int32)
-        off[1:] = np.cumsum(lens)
         top_id = torch.empty((B, max(int(k), 0)), dtype=torch.int32, device=self.device)
         top_lp = torch.empty((B, max(int(k), 0)), dtype=torch.float32, device=self.device)
-        d_type = self._set_types(_padded_types(token_type_ids, keep))      # noqa: F841
+        d_type = self._set_types(types)      # noqa: F841
         _lib.check(self.lib.rs_masked_topk(self.handle, _lib.ptr(d_ids), off.ctypes.data, mp.ctypes.data, B, int(k),
                                            _lib.ptr(top_id), _lib.ptr(top_lp), _lib.stream_ptr(self.device)))
         return top_id, top_lp
@@ -269,10 +267,8 @@ class PLLScorer(BertEngine):
 
         Returns (ids int32 [R, k], logprob float32 [R, k]) device tensors, followed by
         (pll float64 [H], rows float32 [R]) — bitwise ``score_nbest``'s — when ``return_pll``."""
-        off = np.ascontiguousarray(hyp_off, np.int32)
-        n_hyp = len(off) - 1
-        d_tok = self._dev_tokens(tokens)
-        n_rows = int((np.diff(off) - 2).sum()) if n_hyp else 0
+        d_tok, off, n_hyp = self._hyps(tokens, hyp_off)
+        n_rows = _word_rows(off)
         pll = torch.empty(n_hyp, dtype=torch.float64, device=self.device) if return_pll else None
         rows = torch.empty(n_rows, dtype=torch.float32, device=self.device) if return_pll else None
         top_id = torch.empty((n_rows, max(int(k), 0)), dtype=torch.int32, device=self.device)
@@ -292,11 +288,7 @@ class PLLScorer(BertEngine):
         d_ids = torch.from_numpy(np.concatenate([np.asarray(s, np.int32) for s in seqs])).to(self.device)
         mp = np.asarray([r["mask_pos"] for r in rows], np.int32)
         lab = torch.from_numpy(np.asarray([r["labels"][r["mask_pos"]] for r in rows], np.int32)).to(self.device)
-        out = torch.empty(len(rows), dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.rs_masked_logprob(self.handle, _lib.ptr(d_ids), off.ctypes.data, mp.ctypes.data,
-                                              _lib.ptr(lab), len(rows), _lib.ptr(out),
-                                              _lib.stream_ptr(self.device)))
-        return out
+        return self._masked_logprob(d_ids, off, mp, lab)
 
     def run_one_epoch(self, rows, output_score: dict) -> dict:
         """Mirror of ``run_one_epoch(..., train_mode=False, do_scoring=True)``
@@ -318,9 +310,7 @@ class RescoreBertScorer(BertEngine):
         super().__init__(weights, shape, _lib.RS_HEAD_CLS, device, max_rows, precision)
 
     def score_nbest(self, tokens, hyp_off, token_types=None) -> torch.Tensor:
-        off = np.ascontiguousarray(hyp_off, np.int32)
-        n = len(off) - 1
-        d_tok = self._dev_tokens(tokens)
+        d_tok, off, n = self._hyps(tokens, hyp_off)
         out = torch.empty(n, dtype=torch.float32, device=self.device)
         d_type = self._set_types(token_types)      # noqa: F841
         _lib.check(self.lib.rs_cls_score(self.handle, _lib.ptr(d_tok), off.ctypes.data, n,
@@ -343,16 +333,10 @@ class RescoreBertHIP(torch.nn.Module):
         self.engine = RescoreBertScorer(weights, shape, device, max_rows, precision)
 
     def forward(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, token_type_ids=None) -> torch.Tensor:
-        lens = _prefix_lengths(attention_mask)
-        if (lens == 0).any():
+        d_ids, off, types = _ragged(input_ids, attention_mask, token_type_ids, self.engine.device)
+        if (np.diff(off) == 0).any():
             raise ValueError("every row needs at least one attended token")
-        dev = self.engine.device
-        ids = input_ids.to(dev)
-        T = ids.shape[1]
-        keep = torch.arange(T, device=dev)[None, :] < torch.from_numpy(lens).to(dev)[:, None]
-        off = np.zeros(len(lens) + 1, np.int32)
-        off[1:] = np.cumsum(lens)
-        return self.engine.score_nbest(ids[keep].to(torch.int32), off, token_types=_padded_types(token_type_ids, keep))
+        return self.engine.score_nbest(d_ids, off, token_types=types)
 
 
 def pll_of(weights, nb: NBest, shape: BertShape = BERT_BASE, device=0) -> np.ndarray:

@@ -94,18 +94,13 @@ class _Trainer:
         self.extra = {k: np.asarray(v) for k, v in weights.items()
                       if k.startswith("bert.pooler.") or (self.HEAD == "mlm" and k.startswith("cls.predictions.decoder."))}
         heads = _lib.RS_HEAD_CLS if self.HEAD == "cls" else _lib.RS_HEAD_MLM
-        cfg = _lib.RsBertCfg(shape.vocab, shape.hidden, shape.layers, shape.heads, shape.intermediate,
-                             shape.max_pos, shape.type_vocab, shape.ln_eps, shape.mask_id, heads, 0)
+        cfg = _lib.bert_cfg(shape, heads)
         h = ctypes.c_void_p()
         _lib.check(self.lib.rs_trainer_create(ctypes.byref(cfg), self.device.index, ctypes.byref(h)))
         self.handle = h
         try:
-            for k, v in weights.items():
-                if k not in self.shapes:          # e.g. an MLM head when initialising from BertForMaskedLM
-                    continue
-                a = np.ascontiguousarray(v, dtype=np.float32)
-                shp = (ctypes.c_int64 * a.ndim)(*a.shape)
-                _lib.check(self.lib.rs_trainer_set_tensor(self.handle, k.encode(), a.ctypes.data, 0, shp, a.ndim))
+            # (only the trainer's own tensors: not e.g. an MLM head when initialising from BertForMaskedLM)
+            _lib.upload_tensors(self.lib.rs_trainer_set_tensor, self.handle, weights, self.shapes)
             _lib.check(self.lib.rs_trainer_finalize(self.handle))
         except Exception:
             self.close()
