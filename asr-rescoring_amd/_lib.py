@@ -61,6 +61,8 @@ _SIGS = {
     "rs_model_reserve": (ctypes.c_int, [P, I64]),
     "rs_pll_score": (ctypes.c_int, [P, P, P, I32, P, P, P]),
     "rs_pll_score_spans": (ctypes.c_int, [P, P, P, I32, P, P, P, P, P, P, P]),
+    "rs_pll_score_sets": (ctypes.c_int, [P, P, P, I32, P, P, P, P, P, P]),
+    "rs_masked_logprob_multi": (ctypes.c_int, [P, P, P, I32, P, P, P, P, P]),
     "rs_masked_logprob": (ctypes.c_int, [P, P, P, P, P, I32, P, P]),
     "rs_masked_topk": (ctypes.c_int, [P, P, P, P, I32, I32, P, P, P]),
     "rs_pll_topk": (ctypes.c_int, [P, P, P, I32, I32, P, P, P, P, P]),

@@ -15,7 +15,7 @@ generator when ``random_init_seed`` is set.  The tokenizer is ``BertTokenizer``-
 per-character for CJK (``data.CharTokenizer``) built from the data, unless ``model.vocab``
 names a ``vocab.txt`` — then the native BertTokenizer-compatible ``frontend.NativeTokenizer``
 (and score JSON is written by the native ``frontend.json_saving``).  Extra keys: ``precision`` (fp16 / fp16x3), ``max_rows``,
-``mode`` (rescore fusion formula: norm / legacy / am_norm), ``pll_variant`` (mlm_pll: original / word_l2r / whole_word),
+``mode`` (rescore fusion formula: norm / legacy / am_norm), ``pll_variant`` (mlm_pll: original / word_l2r / whole_word), ``pll_stride`` (mlm_pll: strided PLL approximation),
 ``{split}_context_text_path`` (mlm_pll, mlm_topk, rescorebert, rescorebert_train: JSON ``{utt_id: text}``; every
 hypothesis of the utterance becomes the pair ``[CLS] context [SEP] hypothesis [SEP]`` with segment ids 0 / 1,
 ``data.with_context``; a missing utterance has no context; MLM scores cover the hypothesis half only).
@@ -121,6 +121,9 @@ def mlm_pll(cfg) -> Dict[str, str]:
     Ivanova 2023; ``data.pll_spans`` over the word boundaries of the native tokenizer's WordPiece output).
     Extra key ``{split}_context_text_path`` (text inputs only): the hypotheses are scored as the second
     segment of ``[CLS] context [SEP] hypothesis [SEP]``, at the hypothesis' positions only.
+    Extra key ``pll_stride`` (text inputs only, ``pll_variant`` original; absent or 0: exact PLL): k >= 1
+    scores the strided approximation (``data.pll_strided``: every k-th token masked in one copy, all of
+    them scored from it — ``min(k, L)`` forwards per hypothesis instead of L).
 
     Launched with torchrun (WORLD_SIZE > 1): one process per GPU, each scores a contiguous,
     cost-balanced utterance range (``shard.plan_shards``); the scores meet in one all-gather
@@ -128,6 +131,17 @@ def mlm_pll(cfg) -> Dict[str, str]:
     from . import shard
     from .scorer import PLLScorer
     variant, noted = _pll_variant(cfg), False
+    stride = int(get(cfg, "pll_stride", 0) or 0)
+    if stride < 0:
+        raise ValueError("pll_stride must be >= 0")
+    if stride and variant != "original":
+        raise ValueError(f"pll_stride applies to pll_variant original, not {variant!r}")
+    if stride:
+        for split in ("train", "dev", "test"):
+            rows_path = get(cfg, f"{split}_data_path")
+            if rows_path and os.path.exists(rows_path):
+                raise ValueError(f"pll_stride needs {split}_hyps_text_path: the rows of "
+                                 f"{split}_data_path are already masked one position each")
     if variant != "original":
         for split in ("train", "dev", "test"):
             rows_path = get(cfg, f"{split}_data_path")
@@ -165,10 +179,12 @@ def mlm_pll(cfg) -> Dict[str, str]:
             if use != "original":
                 nb.word_start = tok.word_starts(nb.tokens)
             nb = _nbest_context(hyps, tok, nb, ctx)
+            if stride:
+                use = "strided"
             both = shard.score_sharded(nb, lambda sub: scorer.score_nbest(sub.tokens, sub.hyp_off, variant=use,
                                                                           word_start=sub.word_start,
                                                                           token_types=sub.token_type,
-                                                                          score_from=sub.score_from))
+                                                                          score_from=sub.score_from, stride=stride))
             pll = both[1].cpu().numpy()
             output_score = {}
             for (u, h), s in zip(keys, pll):

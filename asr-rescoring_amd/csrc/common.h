@@ -148,6 +148,16 @@ struct SeqMeta {
     const int* mask_end;   // end of the [MASK] span [mask_pos, mask_end); -1 = none
 };
 
+// Query list of a multi-mask call (device copy of seq_plan.h QueryList, uploaded with SeqMeta):
+// sequence s scores positions pos[first[s] .. first[s + 1]), ascending; seq[q] is the sequence of
+// query q.  Query q's state row is row q - q0 of its chunk's per-query buffers (q0 = first[s0]).
+struct QueryMeta {
+    const int* first;      // [S + 1]
+    const int* seq;        // [n_q]
+    const int* pos;        // [n_q]
+    const int* label;      // [n_q] label id, -1 = take tokens[tok_off + pos]
+};
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -254,6 +264,24 @@ hipError_t launch_gather_labels(const int* tok, SeqMeta sm, int s0, int s1, int*
                                 hipStream_t st);
 hipError_t launch_lse_finalize(const float2* part, int n_parts, const float* label_logit,
                                int rows, float* out, hipStream_t st);
+// ---- multi-mask rows (query-list calls: several scored positions per sequence) ----
+// embed_ln whose [MASK] test is "t is one of the sequence's query positions" (qm.pos, ascending)
+hipError_t launch_embed_ln_set(const int* tok, const int* type, SeqMeta sm, QueryMeta qm, int s0, int s1, int mask_id,
+                               int vocab, int type_vocab, const float* word, const float* pos, const float* typetab,
+                               const float* g, const float* b, float eps, int H, float* x32, float2* stats, f16* h16,
+                               int kx, hipStream_t st);
+// launch_attention_query over every query of sequences [s0, s1): ctxq / resq row q - qm.first[s0];
+// qd: dense Q rows in the same order
+hipError_t launch_attention_mquery(const void* qkv, bool qkv32, const float* x32, const float2* stats, const float* g,
+                                   const float* b, SeqMeta sm, QueryMeta qm, int s0, int s1, int H, int heads,
+                                   f16* ctxq, float* resq, int kx, hipStream_t st, const void* qd = nullptr,
+                                   const f16* himg = nullptr);
+// dst[q - q0] = src[row of query q's (sequence, position)], queries [q0, q0 + n)
+hipError_t launch_gather_query_rows_list(const f16* src, int ld, SeqMeta sm, QueryMeta qm, int q0, int n, f16* dst,
+                                        hipStream_t st);
+// launch_gather_labels over queries [q0, q0 + n): qm.label, -1 = the token at the query's position
+hipError_t launch_gather_labels_list(const int* tok, SeqMeta sm, QueryMeta qm, int q0, int n, int* lab,
+                                     float* label_logit, hipStream_t st);
 
 // The MLM decoder over one state row per sequence of [s0, s0 + m_valid): out[i] =
 // log_softmax(A[i] . W^T + bias)[label of sequence s0 + i] over the first `vocab` of vpad columns.
@@ -272,12 +300,17 @@ struct MlmDecoder {
     float2* part;
     float* llog;
     float* out;            // [m_valid]
+    // query-list calls: the rows are queries [s0, s0 + m_valid) of qm (launch_gather_labels_list)
+    const QueryMeta* qm = nullptr;
 };
 // wrap(is_gemm, launch) runs one launch and returns its error: the scorer's profiler scopes
 // (rs_api.hip head_mlm), or a plain call (the rs_debug_decoder test entry)
 template <class Wrap>
 hipError_t launch_mlm_decoder(const MlmDecoder& d, hipStream_t st, Wrap&& wrap) {
-    if (hipError_t e = wrap(false, [&] { return launch_gather_labels(d.tok, d.sm, d.s0, d.s0 + d.m_valid, d.lab, d.llog, st); }))
+    if (hipError_t e = wrap(false, [&] {
+            return d.qm ? launch_gather_labels_list(d.tok, d.sm, *d.qm, d.s0, d.m_valid, d.lab, d.llog, st)
+                        : launch_gather_labels(d.tok, d.sm, d.s0, d.s0 + d.m_valid, d.lab, d.llog, st);
+        }))
         return e;
     EpiArgs ep{};
     ep.bias = d.bias; ep.m_valid = d.m_valid; ep.n_valid = d.vocab; ep.lse_part = d.part;

@@ -18,7 +18,9 @@
 //  fp16   <= 64    attn16_kernel<DEDUP>           16x16x32 MFMA tiles
 //  fp16   >  64    attn_tr_kernel<DEDUP>          32x32x16 MFMA tiles, online softmax
 //
-// attention_query is attn_query_kernel<float | f16>.  attn_memskel_kernel is a timing
+// attention_query is attn_query_kernel<float | f16>; attention_mquery (multi-mask rows: several
+// scored rows per sequence) is attn_mquery_kernel<float | f16>, four waves per (sequence, head), each
+// serving one query at a time in attn_query_kernel's form.  attn_memskel_kernel is a timing
 // diagnostic (rs_debug_attention), not part of the scoring path.
 //
 // rs_debug_attention kinds (AttnKind): 0 attn_tr_kernel, 6 attn16_kernel (fp16 qkv [rows, 3H],
@@ -672,6 +674,76 @@ attn_query_kernel(const QT* __restrict__ qkv, const QT* __restrict__ qd, const f
     }
 }
 
+// Last layer of a multi-mask call: one block of four waves per (sequence, head) serves all of the
+// sequence's query rows, wave w the queries w, w + 4, ... of the sequence's list, one at a time and
+// each with attn_query_kernel's expression order (lanes over keys for QK^T, lanes over the head
+// dims for P.V, 64-key blocks with online softmax), so a query's value does not depend on the
+// sequence's other queries.  The four waves re-read the head's K / V rows (T x 128 values, L2
+// resident after the first wave); every wave owns one 64-float slice of sq / sp.  The trip counts
+// (queries / 4 rounded up, key blocks) are the block's, so every wave reaches every barrier; a
+// wave past the list's end recomputes the sequence's first query and stores nothing.
+template <class QT>
+__global__ void __launch_bounds__(256)
+attn_mquery_kernel(const QT* __restrict__ qkv, const QT* __restrict__ qd, const float* __restrict__ x32,
+                   const float2* __restrict__ stats, const float* __restrict__ lg, const float* __restrict__ lb,
+                   SeqMeta sm, QueryMeta qm, int s0, int H, f16* __restrict__ ctxq, float* __restrict__ resq, int kx,
+                   const f16* __restrict__ himg) {
+    __shared__ float sq[4][64];
+    __shared__ float sp[4][64];
+    const int s = s0 + blockIdx.x, h = blockIdx.y;
+    const int T = sm.len[s], rs = sm.row[s];
+    const int qa = qm.first[s], nqs = qm.first[s + 1] - qa, q0 = qm.first[s0];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int ld = 3 * H;
+    const QT* base = qkv + (size_t)rs * ld + h * 64;
+    for (int i0 = 0; i0 < nqs; i0 += 4) {
+        const bool on = i0 + w < nqs;
+        const int q = qa + (on ? i0 + w : 0);
+        const int qi = qm.pos[q], q_loc = q - q0;
+        __syncthreads();
+        // qd: dense [query, H] rows (the last layer projects Q for the scored rows only)
+        sq[w][lane] = (float)(qd ? qd[(size_t)q_loc * H + h * 64 + lane] : base[(size_t)qi * ld + lane]) * 0.125f;
+        __syncthreads();
+        float m = -INFINITY, l = 0.f, acc = 0.f;
+        for (int k0 = 0; k0 < T; k0 += 64) {
+            const int j = k0 + lane;
+            float sc = -INFINITY;
+            if (j < T) {
+                const QT* kr = base + (size_t)j * ld + H;
+                float d = 0.f;
+#pragma unroll
+                for (int c = 0; c < 8; ++c) {
+                    float kv[8];
+                    load8(kr + c * 8, kv);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) d += sq[w][c * 8 + e] * kv[e];
+                }
+                sc = d;
+            }
+            const float mn = fmaxf(m, wave_max(sc));
+            const float p = (j < T) ? __expf(sc - mn) : 0.f;
+            const float alpha = __expf(m - mn);
+            l = l * alpha + wave_sum(p);
+            acc *= alpha;
+            __syncthreads();
+            sp[w][lane] = p;
+            __syncthreads();
+            const int nk = min(64, T - k0);
+            for (int jj = 0; jj < nk; ++jj)
+                acc += sp[w][jj] * (float)base[(size_t)(k0 + jj) * ld + 2 * H + lane];
+            m = mn;
+        }
+        if (on) {
+            put_split(ctxq + (size_t)q_loc * kx * H, h * 64 + lane, H, kx, acc / l);
+            // residual of the scored row: LN of its pre-LN sum, or the normalised state's image
+            const int c = h * 64 + lane;
+            const size_t r = (size_t)(rs + qi);
+            const float2 hl = himg ? il_parts(himg + r * 2 * H, c) : make_float2(0.f, 0.f);
+            resq[(size_t)q_loc * H + c] = himg ? hl.x + hl.y * X3_DOWN : ln_apply(x32[r * H + c], stats[r], lg[c], lb[c]);
+        }
+    }
+}
+
 // Diagnostic: the memory skeleton of attn_tr_kernel (same Q/K/V reads per (sequence, head)
 // wave, ctx written) with no math — the access pattern's own cost.
 __global__ void __launch_bounds__(256)
@@ -751,6 +823,19 @@ hipError_t launch_attention_query(const void* qkv, bool qkv32, const float* x32,
         hipLaunchKernelGGL(attn_query_kernel<float>, grid, dim3(64), 0, st, (const float*)qkv, (const float*)qd, x32, stats, g, b, sm, s0, row0, H, ctxq, resq, kx, himg);
     else
         hipLaunchKernelGGL(attn_query_kernel<f16>, grid, dim3(64), 0, st, (const f16*)qkv, (const f16*)qd, x32, stats, g, b, sm, s0, row0, H, ctxq, resq, kx, himg);
+    return hipGetLastError();
+}
+
+hipError_t launch_attention_mquery(const void* qkv, bool qkv32, const float* x32, const float2* stats, const float* g,
+                                   const float* b, SeqMeta sm, QueryMeta qm, int s0, int s1, int H, int heads,
+                                   f16* ctxq, float* resq, int kx, hipStream_t st, const void* qd, const f16* himg) {
+    if (s1 <= s0) return hipSuccess;
+    if (H != heads * 64) return hipErrorInvalidValue;
+    const dim3 grid(s1 - s0, heads);
+    if (qkv32)
+        hipLaunchKernelGGL(attn_mquery_kernel<float>, grid, dim3(256), 0, st, (const float*)qkv, (const float*)qd, x32, stats, g, b, sm, qm, s0, H, ctxq, resq, kx, himg);
+    else
+        hipLaunchKernelGGL(attn_mquery_kernel<f16>, grid, dim3(256), 0, st, (const f16*)qkv, (const f16*)qd, x32, stats, g, b, sm, qm, s0, H, ctxq, resq, kx, himg);
     return hipGetLastError();
 }
 

@@ -2,6 +2,7 @@
 //
 //  embed_ln        K1+K2: on-device [MASK] expansion (MLM_PLL/preprocess.py:15-21) fused with
 //                  BertEmbeddings (modeling_bert.py:53-108): word + type[segment id, 0 without] + position -> LN
+//  embed_ln_set    the same for multi-mask rows: [MASK] at every position of the row's query list
 //  ln_rows         LayerNorm of BertSelfOutput / BertOutput / head transform (eps 1e-12)
 //  lse_finalize    merges the decoder epilogue's (max, sum exp) slabs: log_softmax gather
 //                  (MLM_PLL/main.py:101-105)
@@ -120,6 +121,40 @@ embed_ln_kernel(const int* __restrict__ tok, const int* __restrict__ type, SeqMe
     for (int t = wave; t < T; t += 4) {
         float4 x[NV];
         embed_row<NV>(tok, type, toff, t, lo, hi, mask_id, vocab, type_vocab, word, pos, typetab, lane, x);
+        const size_t r = (size_t)(rs + t);
+#pragma unroll
+        for (int v = 0; v < NV; ++v) if (x32) *(float4*)(x32 + r * H + v * 256 + lane * 4) = x[v];
+        ln_store<NV>(x, g, b, eps, lane, nullptr, stats ? stats + r : nullptr, h16 ? h16 + r * kx * H : nullptr, kx);
+    }
+}
+
+// embed_ln for multi-mask rows: position t is [MASK] when it is one of the sequence's query
+// positions (qm.pos[qm.first[s] .. qm.first[s + 1]), strictly ascending: binary search).  The row
+// goes through embed_row / ln_store as in embed_ln_kernel, so a row masked at one position has the
+// bits that kernel gives it.
+template <int NV>
+__global__ void __launch_bounds__(256)
+embed_ln_set_kernel(const int* __restrict__ tok, const int* __restrict__ type, SeqMeta sm, QueryMeta qm, int s0,
+                    int mask_id, int vocab, int type_vocab, const float* __restrict__ word,
+                    const float* __restrict__ pos, const float* __restrict__ typetab, const float* __restrict__ g,
+                    const float* __restrict__ b, float eps, float* __restrict__ x32, float2* __restrict__ stats,
+                    f16* __restrict__ h16, int kx) {
+    constexpr int H = NV * 256;
+    const int s = s0 + blockIdx.x;
+    const int T = sm.len[s], toff = sm.tok_off[s], rs = sm.row[s];
+    const int qa = qm.first[s], qb = qm.first[s + 1];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int t = wave; t < T; t += 4) {
+        int lo = qa, hi = qb;                      // first query position >= t
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (qm.pos[mid] < t) lo = mid + 1;
+            else hi = mid;
+        }
+        const bool masked = lo < qb && qm.pos[lo] == t;
+        float4 x[NV];
+        embed_row<NV>(tok, type, toff, t, masked ? t : -1, masked ? t + 1 : -1, mask_id, vocab, type_vocab, word, pos,
+                      typetab, lane, x);
         const size_t r = (size_t)(rs + t);
 #pragma unroll
         for (int v = 0; v < NV; ++v) if (x32) *(float4*)(x32 + r * H + v * 256 + lane * 4) = x[v];
@@ -309,6 +344,27 @@ __global__ void gather_labels_kernel(const int* __restrict__ tok, SeqMeta sm, in
     const int s = s0 + i;
     const int l = sm.label[s];
     lab[i] = (l == -1 && tok) ? tok[sm.tok_off[s] + sm.query[s]] : l;
+    label_logit[i] = -INFINITY;
+}
+
+// The two gathers over a query list: block / thread i serves query q0 + i, whose row is
+// (sequence qm.seq, position qm.pos).
+__global__ void __launch_bounds__(64)
+gather_query_rows_list_kernel(const f16* __restrict__ src, int ld, SeqMeta sm, QueryMeta qm, int q0,
+                              f16* __restrict__ dst) {
+    const int q = q0 + blockIdx.x;
+    const size_t r = (size_t)(sm.row[qm.seq[q]] + qm.pos[q]);
+    const uint4* a = (const uint4*)(src + r * ld);
+    uint4* o = (uint4*)(dst + (size_t)blockIdx.x * ld);
+    for (int i = threadIdx.x; i < ld / 8; i += 64) o[i] = a[i];
+}
+__global__ void gather_labels_list_kernel(const int* __restrict__ tok, SeqMeta sm, QueryMeta qm, int q0, int n,
+                                          int* __restrict__ lab, float* __restrict__ label_logit) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int q = q0 + i;
+    const int l = qm.label[q];
+    lab[i] = (l == -1 && tok) ? tok[sm.tok_off[qm.seq[q]] + qm.pos[q]] : l;
     label_logit[i] = -INFINITY;
 }
 
@@ -546,6 +602,34 @@ hipError_t launch_gather_labels(const int* tok, SeqMeta sm, int s0, int s1, int*
     const int n = s1 - s0;
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(gather_labels_kernel, dim3((n + 255) / 256), dim3(256), 0, st, tok, sm, s0, n, lab, label_logit);
+    return hipGetLastError();
+}
+
+hipError_t launch_embed_ln_set(const int* tok, const int* type, SeqMeta sm, QueryMeta qm, int s0, int s1, int mask_id,
+                               int vocab, int type_vocab, const float* word, const float* pos, const float* typetab,
+                               const float* g, const float* b, float eps, int H, float* x32, float2* stats, f16* h16,
+                               int kx, hipStream_t st) {
+    const int n = s1 - s0;
+    if (n <= 0) return hipSuccess;
+    return launch_for_h(H, [&](auto nv) {
+        hipLaunchKernelGGL(embed_ln_set_kernel<decltype(nv)::value>, dim3(n), dim3(256), 0, st, tok, type, sm, qm, s0,
+                           mask_id, vocab, type_vocab, word, pos, typetab, g, b, eps, x32, stats, h16, kx);
+    });
+}
+
+hipError_t launch_gather_query_rows_list(const f16* src, int ld, SeqMeta sm, QueryMeta qm, int q0, int n, f16* dst,
+                                        hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    if (ld % 8) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gather_query_rows_list_kernel, dim3(n), dim3(64), 0, st, src, ld, sm, qm, q0, dst);
+    return hipGetLastError();
+}
+
+hipError_t launch_gather_labels_list(const int* tok, SeqMeta sm, QueryMeta qm, int q0, int n, int* lab,
+                                     float* label_logit, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(gather_labels_list_kernel, dim3((n + 255) / 256), dim3(256), 0, st, tok, sm, qm, q0, n, lab,
+                       label_logit);
     return hipGetLastError();
 }
 

@@ -418,6 +418,9 @@ struct Call {
     int topk_k = 0;
     int32_t* topk_id = nullptr;
     float* topk_lp = nullptr;
+    // multi-mask rows: several scored positions per sequence (seq_plan.h QueryList); the last layer
+    // and the head then run one row per query, out_rows holds one float per query
+    const QueryList* ql = nullptr;
 };
 
 // The environment switches of one scoring call: read once (call_opts, at the top of run_all) and
@@ -481,7 +484,7 @@ CallOpts call_opts(const rs_model* m) {
 }
 
 // One chunk's run of the encoder + head over sequences [c.s0, c.s1): what the call fixed, and the
-// typed workspace pointers.  Aggregate: the first six members are given, the rest follow.
+// typed workspace pointers.  Aggregate: the first seven members are given, the rest follow.
 struct ChunkCtx {
     rs_model* m;
     hipStream_t st;
@@ -489,12 +492,17 @@ struct ChunkCtx {
     const SeqMeta& sm;
     const Chunk& c;
     const CallOpts& o;
+    const QueryMeta& qm;                      // query-list calls (call.ql), else unused
     const rs_bert_cfg& cf = m->cfg;
     const int H = cf.hidden, F = cf.intermediate, nh = cf.heads, kx = m->kx;
     const float eps = cf.ln_eps;
     const bool q32 = kx == 3;                 // fp16x3: QKV kept in fp32 for attention
     const int qkv_epi = q32 ? EPI_BIAS_F32 : EPI_BIAS_F16;   // (split-operand layers are fp16x3: fp32)
     const int rows = c.rows, ns = c.s1 - c.s0;
+    // rows of the query-row-only layer and the head, and the first of them in the call's output:
+    // one per sequence, or (query-list calls) one per query
+    const bool mq = call.ql != nullptr;
+    const int nr = mq ? c.nq : ns, r0 = mq ? c.q0 : c.s0;
     const bool dedup = c.urows > 0;           // layer-0 Q/K/V over unique rows (MLM; fp16, or fp16x3 split)
     const int kxf = o.x3s ? 2 : kx;           // width factor of the full-row operand images (split: two-part)
     float2 *xst = m->xst.as<float2>(), *xst1 = m->xst1.as<float2>();
@@ -502,7 +510,7 @@ struct ChunkCtx {
     f16* h16 = m->h16.as<f16>();              // ... or, with imgres, its image here
     void* qkv = m->qkv.p;
     f16 *ctx = m->ctx.as<f16>(), *inter = m->inter.as<f16>();
-    // one row per sequence (query-row-only layer and heads)
+    // one row per sequence or query (query-row-only layer and heads)
     f16 *ctxq = m->ctxq.as<f16>(), *hq16 = m->hq16.as<f16>(), *interq = m->interq.as<f16>();
     float *resq = m->resq.as<float>(), *tq = m->tq32.as<float>(), *hq32 = m->hq32.as<float>();
 
@@ -548,6 +556,13 @@ struct ChunkCtx {
         // residual — and the unique rows' image goes to the idle FFN buffer)
         // (segment ids, call.d_type: indexed like d_tok, so a unique row, keyed by hypothesis and
         // position, has one type and the plan is the same with and without them)
+        // (multi-mask rows: the [MASK] set is the sequence's query list; never with dedup)
+        if (mq && call.ql->masked) {
+            TRY_HIP(launch_embed_ln_set(call.d_tok, call.d_type, sm, qm, c.s0, c.s1, cf.mask_id, cf.vocab, cf.type_vocab,
+                                       m->word32, m->pos32, m->type32, m->eg, m->eb, eps, H, o.imgres ? nullptr : t32,
+                                       o.imgres ? nullptr : xst, h16, kxf, st));
+            return RS_OK;
+        }
         TRY_HIP(launch_embed_ln(call.d_tok, call.d_type, sm, c.s0, c.s1, 0, cf.mask_id, cf.vocab, cf.type_vocab, m->word32,
                                m->pos32, m->type32, m->eg, m->eb, eps, H, o.imgres ? nullptr : t32,
                                o.imgres ? nullptr : xst, dedup && !o.x3s ? nullptr : h16, kxf, st));
@@ -570,12 +585,13 @@ struct ChunkCtx {
             return gemm(RS_K_QKV, qkv_epi, sp, uq && sp ? inter : h16, W, uq ? c.urows : rows, 3 * H, K,
                         bias_ep(L.bqkv, qkv, 3 * H), last ? 2 * H : 3 * H);
         // K and V for every row (rows H..3H of the fused weight, written into columns H..3H of
-        // qkv), Q only for the scored row of each sequence (gathered operand rows -> dense
-        // [sequence, H] in the idle tq32 buffer)
+        // qkv), Q only for the scored row(s) of each sequence (gathered operand rows -> dense
+        // [sequence or query, H] in the idle tq32 buffer)
         if (int r = gemm(RS_K_QKV, qkv_epi, sp, h16, W + (size_t)H * ldw, rows, 2 * H, K,
                          bias_ep(L.bqkv + H, (char*)qkv + H * (size_t)(q32 ? 4 : 2), 3 * H), 2 * H)) return r;
-        LAUNCH_OTHER(launch_gather_query_rows(h16, kxf * H, sm, c.s0, c.s1, 0, hq16, st));
-        return gemm(RS_K_QKV, qkv_epi, sp, hq16, W, ns, H, K, bias_ep(L.bqkv, tq, H), H);
+        if (mq) LAUNCH_OTHER(launch_gather_query_rows_list(h16, kxf * H, sm, qm, c.q0, c.nq, hq16, st));
+        else LAUNCH_OTHER(launch_gather_query_rows(h16, kxf * H, sm, c.s0, c.s1, 0, hq16, st));
+        return gemm(RS_K_QKV, qkv_epi, sp, hq16, W, nr, H, K, bias_ep(L.bqkv, tq, H), H);
     }
 
     // Residual block of the split-operand layer: h16 <- image(LN(A·Wᵀ + b + h16)) in the GEMM
@@ -653,26 +669,30 @@ struct ChunkCtx {
         return RS_OK;
     }
 
-    // Last layer of the scoring modes: only the scored row of every sequence (one row per sequence)
+    // Last layer of the scoring modes: only the scored rows (one per sequence, or one per query)
     int layer_query(int li, bool qrow) {
         const Layer& L = m->layers[li];
-        LAUNCH(RS_K_ATTN, launch_attention_query(qkv, q32, t32, xst, prev_g(li), prev_b(li), sm, c.s0, c.s1, 0, H, nh,
-                                                 ctxq, resq, kx, st, qrow ? tq : nullptr, o.imgres ? h16 : nullptr));
-        if (int r = gemm(RS_K_OPROJ, EPI_RES_F32, false, ctxq, L.wo, ns, H, kx * H, bias_ep(L.bo, tq, H, resq), H))
+        if (mq)
+            LAUNCH(RS_K_ATTN, launch_attention_mquery(qkv, q32, t32, xst, prev_g(li), prev_b(li), sm, qm, c.s0, c.s1, H, nh,
+                                                      ctxq, resq, kx, st, qrow ? tq : nullptr, o.imgres ? h16 : nullptr));
+        else
+            LAUNCH(RS_K_ATTN, launch_attention_query(qkv, q32, t32, xst, prev_g(li), prev_b(li), sm, c.s0, c.s1, 0, H, nh,
+                                                     ctxq, resq, kx, st, qrow ? tq : nullptr, o.imgres ? h16 : nullptr));
+        if (int r = gemm(RS_K_OPROJ, EPI_RES_F32, false, ctxq, L.wo, nr, H, kx * H, bias_ep(L.bo, tq, H, resq), H))
             return r;
-        LAUNCH_OTHER(launch_ln_rows(tq, ns, L.g1, L.be1, eps, H, hq32, nullptr, hq16, kx, st));
-        if (int r = gemm(RS_K_FFN1, EPI_GELU_F16, false, hq16, L.w1, ns, F, kx * H, gelu_ep(L.b1, interq, kx), F)) return r;
-        if (int r = gemm(RS_K_FFN2, EPI_RES_F32, false, interq, L.w2, ns, H, kx * F, bias_ep(L.b2, tq, H, hq32), H))
+        LAUNCH_OTHER(launch_ln_rows(tq, nr, L.g1, L.be1, eps, H, hq32, nullptr, hq16, kx, st));
+        if (int r = gemm(RS_K_FFN1, EPI_GELU_F16, false, hq16, L.w1, nr, F, kx * H, gelu_ep(L.b1, interq, kx), F)) return r;
+        if (int r = gemm(RS_K_FFN2, EPI_RES_F32, false, interq, L.w2, nr, H, kx * F, bias_ep(L.b2, tq, H, hq32), H))
             return r;
-        LAUNCH_OTHER(launch_ln_rows(tq, ns, L.g2, L.be2, eps, H, hq32, nullptr, hq16, kx, st));
+        LAUNCH_OTHER(launch_ln_rows(tq, nr, L.g2, L.be2, eps, H, hq32, nullptr, hq16, kx, st));
         return RS_OK;
     }
 
     int head_mlm() {
-        if (int r = gemm(RS_K_DECODER, EPI_GELU_F32, false, hq16, m->wt, ns, H, kx * H, bias_ep(m->bt, tq, H), H)) return r;
-        LAUNCH_OTHER(launch_ln_rows(tq, ns, m->gt, m->bet, eps, H, hq32, nullptr, hq16, kx, st));
-        const MlmDecoder d{hq16, m->wdec, m->bdec, ns, m->vpad, cf.vocab, kx * H, call.d_tok, sm, c.s0, m->lab.as<int>(),
-                           m->part.as<float2>(), m->llog.as<float>(), call.out_rows + c.s0};
+        if (int r = gemm(RS_K_DECODER, EPI_GELU_F32, false, hq16, m->wt, nr, H, kx * H, bias_ep(m->bt, tq, H), H)) return r;
+        LAUNCH_OTHER(launch_ln_rows(tq, nr, m->gt, m->bet, eps, H, hq32, nullptr, hq16, kx, st));
+        const MlmDecoder d{hq16, m->wdec, m->bdec, nr, m->vpad, cf.vocab, kx * H, call.d_tok, sm, r0, m->lab.as<int>(),
+                           m->part.as<float2>(), m->llog.as<float>(), call.out_rows + r0, mq ? &qm : nullptr};
         if (call.topk_k) {
             // the only fork of a top-k call: the decoder launcher (its GEMM runs in n_gemm sub-batches)
             const int k = call.topk_k, n_gemm = (ns + TOPK_SUB_ROWS - 1) / TOPK_SUB_ROWS;
@@ -685,7 +705,7 @@ struct ChunkCtx {
             return RS_OK;
         }
         TRY_HIP(launch_mlm_decoder(d, st, [&](bool is_gemm, auto&& launch) {
-            ProfScope ps(m, st, is_gemm ? RS_K_DECODER : RS_K_OTHER, is_gemm ? 2.0 * ns * (double)cf.vocab * (kx * H) : 0);
+            ProfScope ps(m, st, is_gemm ? RS_K_DECODER : RS_K_OTHER, is_gemm ? 2.0 * nr * (double)cf.vocab * (kx * H) : 0);
             return launch();
         }));
         return RS_OK;
@@ -734,14 +754,25 @@ int64_t chunk_cap(const rs_model* m, const CallOpts& o) {
     return cap;
 }
 
-// Chunks of <= cap rows and <= s_cap sequences; sets sl.row (first row of a sequence in its chunk).
-int cut_chunks(const rs_model* m, SeqList& sl, int64_t cap, std::vector<Chunk>* chunks) {
+// Chunks of <= cap rows and <= s_cap sequences (ql: and <= s_cap queries); sets sl.row (first row
+// of a sequence in its chunk).
+int cut_chunks(const rs_model* m, SeqList& sl, const QueryList* ql, int64_t cap, std::vector<Chunk>* chunks) {
     for (int T : sl.len) {
         if (T > m->cfg.max_pos) return fail(RS_EUNSUP, "sequence longer than max_position_embeddings");
         if (T < 1) return fail(RS_EARG, "empty sequence");
         if (T > m->max_rows) return fail(RS_EARG, "sequence longer than the reserved rows");
     }
-    cut_rows(sl, cap, m->s_cap, chunks);
+    if (!ql) {
+        cut_rows(sl, cap, m->s_cap, chunks);
+        return RS_OK;
+    }
+    // query-list call: a chunk's queries fit the per-query workspace (s_cap rows, as its sequences do)
+    const int bad = cut_rows_queries(sl, *ql, cap, m->s_cap, chunks);
+    if (bad >= 0)
+        return fail(RS_EARG, "row " + std::to_string(bad) + " scores " + std::to_string(ql->count(bad)) +
+                                 " positions, the reserved workspace holds " + std::to_string(m->s_cap) +
+                                 " per launch: rs_model_reserve max_rows >= " +
+                                 std::to_string(3 * ((int64_t)ql->count(bad) - 1)) + " would fit it");
     return RS_OK;
 }
 
@@ -755,18 +786,37 @@ void plan_dedup(const rs_model* m, const CallOpts& o, int mode, SeqList& sl, std
 }
 
 // One upload of all metadata through the pinned staging buffer: the nine SeqList columns, then
-// the call's extra ints (-> *call.d_extra); call.d_label: device labels instead of the list's.
-int upload_meta(rs_model* m, hipStream_t st, const Call& call, const SeqList& sl, SeqMeta* sm) {
-    const size_t S = sl.size(), n_extra = call.extra ? call.extra->size() : 0, n_int = 9 * S + n_extra;
+// the call's extra ints (-> *call.d_extra), then the query list (call.ql -> *qm: first [S + 1],
+// and seq, pos, label per query); call.d_label: device labels instead of the list's (per query
+// with a query list, else per sequence).
+int upload_meta(rs_model* m, hipStream_t st, const Call& call, const SeqList& sl, SeqMeta* sm, QueryMeta* qm) {
+    const QueryList* ql = call.ql;
+    const size_t S = sl.size(), n_extra = call.extra ? call.extra->size() : 0, Q = ql ? ql->size() : 0;
+    const size_t n_seq_int = 9 * S + n_extra, n_int = n_seq_int + (ql ? S + 1 + 3 * Q : 0);
     TRY_HIP(m->stage_meta.begin(n_int));
     int* p = m->stage_meta.p;
     const std::vector<int>* cols[9] = {&sl.tok_off, &sl.len, &sl.mask, &sl.query, &sl.label, &sl.row,
                                        &sl.urow_h, &sl.urow_m, &sl.mask_end};
     for (int k = 0; k < 9; ++k) std::memcpy(p + k * S, cols[k]->data(), S * 4);
     if (n_extra) std::memcpy(p + 9 * S, call.extra->data(), n_extra * 4);
+    if (ql) {
+        int* q = p + n_seq_int;
+        std::memcpy(q, ql->first.data(), (S + 1) * 4);
+        int* seq = q + S + 1;
+        for (size_t s = 0; s < S; ++s) std::fill(seq + ql->first[s], seq + ql->first[s + 1], (int)s);
+        std::memcpy(seq + Q, ql->pos.data(), Q * 4);
+        std::memcpy(seq + 2 * Q, ql->label.data(), Q * 4);
+    }
     TRY_HIP(m->stage_meta.upload(m->meta, n_int, st));
     int* d = m->meta.as<int>();
-    if (call.d_label) TRY_HIP(hipMemcpyAsync(d + 4 * S, call.d_label, S * 4, hipMemcpyDeviceToDevice, st));
+    if (ql) {
+        int* q = d + n_seq_int;
+        *qm = QueryMeta{q, q + S + 1, q + S + 1 + Q, q + S + 1 + 2 * Q};
+        if (call.d_label && Q)
+            TRY_HIP(hipMemcpyAsync(q + S + 1 + 2 * Q, call.d_label, Q * 4, hipMemcpyDeviceToDevice, st));
+    } else if (call.d_label) {
+        TRY_HIP(hipMemcpyAsync(d + 4 * S, call.d_label, S * 4, hipMemcpyDeviceToDevice, st));
+    }
     *sm = SeqMeta{d, d + S, d + 2 * S, d + 3 * S, d + 4 * S, d + 5 * S, d + 6 * S, d + 7 * S, d + 8 * S};
     if (call.d_extra) *call.d_extra = d + 9 * S;
     return RS_OK;
@@ -781,12 +831,13 @@ int run_all(rs_model* m, hipStream_t st, const Call& call, SeqList& sl) {
     TRY_HIP(hipSetDevice(m->device));
     if (int r = begin_call(m, st)) return r;
     std::vector<Chunk> chunks;
-    if (int r = cut_chunks(m, sl, chunk_cap(m, opts), &chunks)) return r;
-    plan_dedup(m, opts, call.mode, sl, chunks);
+    if (int r = cut_chunks(m, sl, call.ql, chunk_cap(m, opts), &chunks)) return r;
+    if (!call.ql) plan_dedup(m, opts, call.mode, sl, chunks);   // query-list calls run layer 0 over all rows
     SeqMeta sm{};
-    if (int r = upload_meta(m, st, call, sl, &sm)) return r;
+    QueryMeta qm{};
+    if (int r = upload_meta(m, st, call, sl, &sm, &qm)) return r;
     for (const Chunk& c : chunks) {
-        ChunkCtx cx{m, st, call, sm, c, opts};
+        ChunkCtx cx{m, st, call, sm, c, opts, qm};
         if (int r = cx.run()) return r;
     }
     return RS_OK;
@@ -851,22 +902,44 @@ int rows_whole(const int32_t* h_hyp_off, int n_hyp, SeqList& sl, Check&& check) 
     return RS_OK;
 }
 
-// End of the three PLL entries: the rows' buffer (the caller's, else rowlp_tmp), the run, the
+// End of the PLL entries: the rows' buffer (the caller's, else rowlp_tmp), the run, the
 // float64 sum per hypothesis when d_pll is given, then the finite checks of every output.
+// One output row per sequence, or (call.ql) per query; hso counts the same.
 int pll_tail(rs_model* m, hipStream_t st, Call& call, SeqList& sl, const std::vector<int>& hso, int n_hyp,
              double* d_pll, float* d_row_lp) {
     float* rows = d_row_lp;
+    const size_t n_out = call.ql ? call.ql->size() : sl.size();
     if (!rows) {
-        TRY_HIP(m->rowlp_tmp.ensure(std::max<size_t>(sl.size(), 1) * 4));
+        TRY_HIP(m->rowlp_tmp.ensure(std::max<size_t>(n_out, 1) * 4));
         rows = m->rowlp_tmp.as<float>();
     }
     int* d_hso = nullptr;
     call.out_rows = rows; call.extra = &hso; call.d_extra = &d_hso;
     if (int r = run_all(m, st, call, sl)) return r;
     if (d_pll) LAUNCH_OTHER(launch_segsum_f64(rows, d_hso, n_hyp, d_pll, st));
-    if (!call.topk_k) return check_finite(m, st, rows, sl.size(), "masked-token log-probability");
+    if (!call.topk_k) return check_finite(m, st, rows, n_out, "masked-token log-probability");
     if (int r = mark_nonfinite(m, st, rows, sl.size())) return r;
     return check_finite(m, st, call.topk_lp, sl.size() * call.topk_k, "masked-token or top-k log-probability");
+}
+
+// Opening of the multi-mask entries: the model can run a query-list call (MLM head; the query-row
+// layer is not layer 0).
+int validate_sets(const rs_model* m) {
+    if (int r = validate_call(m, MODE_MLM)) return r;
+    if (m->cfg.layers < 2) return fail(RS_EUNSUP, "multi-mask rows need a model of at least 2 layers");
+    return RS_OK;
+}
+// an offsets array [n + 1]: starts at 0, never descends
+int offsets_ok(const int32_t* off, int n, const char* name) {
+    if (off[0] != 0) return fail(RS_EARG, std::string(name) + "[0] must be 0");
+    for (int i = 0; i < n; ++i)
+        if (off[i + 1] < off[i]) return fail(RS_EARG, std::string(name) + " not ascending at " + std::to_string(i));
+    return RS_OK;
+}
+std::string positions_text(const int32_t* p, int n) {
+    std::string t;
+    for (int i = 0; i < n && i < 8; ++i) t += (i ? ", " : "") + std::to_string(p[i]);
+    return n > 8 ? t + ", ..." : t;
 }
 
 // rs_pll_score / rs_pll_topk after their argument checks: every word position of every hypothesis
@@ -1130,6 +1203,77 @@ int rs_pll_score_spans(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_o
         }
     }
     return pll_tail(m, st, call, sl, hso, n_hyp, d_pll, d_row_lp);
+}
+
+int rs_pll_score_sets(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off, int32_t n_hyp,
+                      const int32_t* h_row_off, const int32_t* h_pos_off, const int32_t* h_pos, double* d_pll,
+                      float* d_pos_lp, void* stream) {
+    PendingTypes ty(m);
+    if (!m || !h_hyp_off || !h_row_off || n_hyp < 0 || (n_hyp > 0 && (!d_tok || !d_pll)))
+        return fail(RS_EARG, "null argument");
+    hipStream_t st = (hipStream_t)stream;
+    if (n_hyp == 0) return RS_OK;
+    if (int r = validate_sets(m)) return r;
+    if (int r = offsets_ok(h_row_off, n_hyp, "row_off")) return r;
+    const int n_rows = h_row_off[n_hyp];
+    if (n_rows > 0 && (!h_pos_off || !h_pos)) return fail(RS_EARG, "null argument");
+    if (n_rows > 0)
+        if (int r = offsets_ok(h_pos_off, n_rows, "pos_off")) return r;
+    Call call{MODE_MLM, d_tok};
+    if (int r = ty.take(h_hyp_off[n_hyp], &call)) return r;
+    CALL_ORDER(m, st);
+    SeqList sl;
+    QueryList ql;
+    ql.masked = true;
+    std::vector<int> hso(n_hyp + 1, 0);                         // hypothesis -> first query
+    for (int h = 0; h < n_hyp; ++h) {
+        const int o = h_hyp_off[h], T = h_hyp_off[h + 1] - o;
+        for (int r = h_row_off[h]; r < h_row_off[h + 1]; ++r) {
+            const int32_t* p = h_pos + h_pos_off[r];
+            const int n = h_pos_off[r + 1] - h_pos_off[r];
+            if (!positions_ok(p, n, 1, T - 2))
+                return fail(RS_EARG, "row " + std::to_string(r) + " (hypothesis " + std::to_string(h) + ", T = " +
+                                         std::to_string(T) + "): need at least one position, strictly ascending, "
+                                         "1 <= p <= T - 2, got " + std::to_string(n) + " [" + positions_text(p, n) + "]");
+            sl.push(o, T, -1, -1, 0, -1);
+            ql.push(p, n, -1);
+        }
+        hso[h + 1] = (int)ql.size();
+    }
+    call.ql = &ql;
+    return pll_tail(m, st, call, sl, hso, n_hyp, d_pll, d_pos_lp);
+}
+
+int rs_masked_logprob_multi(rs_model* m, const int32_t* d_ids, const int32_t* h_seq_off, int32_t n_seq,
+                            const int32_t* h_q_off, const int32_t* h_qpos, const int32_t* d_label, float* d_out,
+                            void* stream) {
+    PendingTypes ty(m);
+    if (!m || !h_seq_off || !h_q_off || n_seq < 0 || (n_seq > 0 && !d_ids)) return fail(RS_EARG, "null argument");
+    if (n_seq == 0) return RS_OK;
+    if (int r = validate_sets(m)) return r;
+    if (int r = offsets_ok(h_q_off, n_seq, "q_off")) return r;
+    // (no query at all: the first row is reported below, whatever the query arrays are)
+    if (h_q_off[n_seq] > 0 && (!h_qpos || !d_label || !d_out)) return fail(RS_EARG, "null argument");
+    Call call{MODE_MLM, d_ids, d_out, d_label};
+    if (int r = ty.take(h_seq_off[n_seq], &call)) return r;
+    hipStream_t st = (hipStream_t)stream;
+    CALL_ORDER(m, st);
+    SeqList sl;
+    QueryList ql;
+    for (int s = 0; s < n_seq; ++s) {
+        const int o = h_seq_off[s], T = h_seq_off[s + 1] - o;
+        const int n = h_q_off[s + 1] - h_q_off[s];
+        const int32_t* p = n ? h_qpos + h_q_off[s] : nullptr;
+        if (!positions_ok(p, n, 0, T - 1))
+            return fail(RS_EARG, "row " + std::to_string(s) + " (T = " + std::to_string(T) +
+                                     "): need at least one query position, strictly ascending, 0 <= p < T, got " +
+                                     std::to_string(n) + " [" + positions_text(p, n) + "]");
+        sl.push(o, T, -1, -1, 0, 0);
+        ql.push(p, n, 0);
+    }
+    call.ql = &ql;
+    if (int r = run_all(m, st, call, sl)) return r;
+    return check_finite(m, st, d_out, ql.size(), "masked-token log-probability");
 }
 
 int rs_masked_logprob(rs_model* m, const int32_t* d_ids, const int32_t* h_seq_off,

@@ -1,6 +1,7 @@
 // Host-side plan of one scoring call: the sequence list, its cut into launch chunks and the
-// layer-0 unique-row plan (dedup).  No HIP types: rs_api.hip includes it, and so does the
-// stand-alone check tests/host/seq_plan_check.cpp, which runs without a GPU.
+// layer-0 unique-row plan (dedup), and the query list of the multi-mask calls with its chunk cut.
+// No HIP types: rs_api.hip includes it, and so do the stand-alone checks
+// tests/host/seq_plan_check.cpp and tests/host/multimask_plan_check.cpp, which run without a GPU.
 //
 // The one function both the host and the device use is unique_rows_owned: which unique rows the
 // embed_unique block of a sequence writes.  The check restates the launch with it and counts the
@@ -31,6 +32,7 @@ struct Chunk {
     int s0, s1, rows;
     int urows = 0;     // layer-0 unique rows (dedup mode), 0 = dedup off for this chunk
     int max_len = 0;   // longest sequence of the chunk (attention kernel choice)
+    int q0 = 0, nq = 0;   // query-list calls (QueryList): first query of the chunk, and their count
 };
 
 // Row r of rs_pll_score_spans: 1 <= lo <= query < hi <= T - 1 ([CLS] and [SEP] are never masked).
@@ -58,6 +60,56 @@ inline void cut_rows(SeqList& sl, long long cap, int s_cap, std::vector<Chunk>* 
         max_len = std::max(max_len, T);
     }
     if (S) chunks->push_back({s0, (int)S, rows, 0, max_len});
+}
+
+// Query list of a multi-mask call (rs_pll_score_sets, rs_masked_logprob_multi), beside the
+// sequence list: sequence s scores the positions pos[first[s] .. first[s + 1]), strictly ascending,
+// each against label[q] (-1: the token at the position).  masked: the positions are also the
+// sequence's [MASK] set (the embedding replaces them on the device); the list's mask / query
+// columns are then unused (-1 / 0).
+struct QueryList {
+    std::vector<int> first{0}, pos, label;   // first: [S + 1] once every sequence is pushed
+    bool masked = false;
+    // the queries of the next sequence: n positions p[0 .. n)
+    void push(const int* p, int n, int lb) {
+        pos.insert(pos.end(), p, p + n);
+        label.insert(label.end(), (size_t)n, lb);
+        first.push_back((int)pos.size());
+    }
+    int count(size_t s) const { return first[s + 1] - first[s]; }
+    size_t size() const { return pos.size(); }
+};
+
+// 0 <= lo <= p[0] < p[1] < ... < p[n - 1] <= hi, n >= 1
+inline bool positions_ok(const int* p, int n, int lo, int hi) {
+    if (n < 1 || p[0] < lo || p[n - 1] > hi) return false;
+    for (int i = 1; i < n; ++i)
+        if (p[i] <= p[i - 1]) return false;
+    return true;
+}
+
+// cut_rows for a query-list call: chunks of <= cap rows, <= s_cap sequences and <= s_cap queries
+// (the per-query workspace holds s_cap rows, as the per-sequence one does); sets sl.row and the
+// chunks' q0 / nq.  A sequence with more than s_cap queries fits no chunk: returns its index
+// (nothing usable in *chunks then), else -1.
+inline int cut_rows_queries(SeqList& sl, const QueryList& ql, long long cap, int s_cap, std::vector<Chunk>* chunks) {
+    const size_t S = sl.size();
+    int rows = 0, s0 = 0, max_len = 0;
+    for (size_t s = 0; s < S; ++s) {
+        const int T = sl.len[s], n = ql.count(s);
+        if (n > s_cap) return (int)s;
+        if (rows + T > cap || (int)s - s0 >= s_cap || ql.first[s + 1] - ql.first[s0] > s_cap) {
+            chunks->push_back({s0, (int)s, rows, 0, max_len, ql.first[s0], ql.first[s] - ql.first[s0]});
+            s0 = (int)s;
+            rows = 0;
+            max_len = 0;
+        }
+        sl.row[s] = rows;
+        rows += T;
+        max_len = std::max(max_len, T);
+    }
+    if (S) chunks->push_back({s0, (int)S, rows, 0, max_len, ql.first[s0], ql.first[S] - ql.first[s0]});
+    return -1;
 }
 
 // Layer-0 dedup (MLM_PLL): the masked copies of one hypothesis share every layer-0 input row

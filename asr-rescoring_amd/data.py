@@ -161,6 +161,39 @@ def pll_spans(hyp_off, word_start, variant: str = "original", score_from=None):
     return (row_off.astype(np.int32), lo.astype(np.int32), hi.astype(np.int32), p.astype(np.int32))
 
 
+def pll_strided(hyp_off, stride: int, score_from=None):
+    """Rows of ``rs_pll_score_sets`` for the strided PLL approximation: a hypothesis with scored
+    positions ``a..L`` (``a = 1``, or ``score_from[h]``; ``n = L - a + 1`` of them) gets rows
+    ``j = 0 .. min(stride, n) - 1``, row j masking AND scoring positions ``a + j, a + j + stride,
+    ...`` from one forward: ``min(stride, n)`` forwards per hypothesis instead of n.  ``stride >= n``
+    gives the singleton rows ``a..L`` in order, the rows of ``rs_pll_score``; a smaller stride
+    conditions every token on a context with 1 / stride of the other tokens hidden as well.
+
+    Returns int32 arrays ``(row_off [H + 1], pos_off [rows + 1], pos)``, positions relative to the
+    hypothesis."""
+    stride = int(stride)
+    if stride < 1:
+        raise ValueError("stride must be >= 1")
+    off = np.asarray(hyp_off, np.int64)
+    if len(off) < 1 or (np.diff(off) < 2).any():
+        raise ValueError("every hypothesis needs [CLS] and [SEP]")
+    L = np.diff(off) - 2
+    a = np.ones(len(L), np.int64)
+    if score_from is not None:
+        a = np.maximum(np.asarray(score_from, np.int64), 1)
+        if len(a) != len(L):
+            raise ValueError("score_from must have one entry per hypothesis")
+    row_off, pos_off, pos = [0], [0], []
+    for h in range(len(L)):
+        n = max(int(L[h] - a[h]) + 1, 0)
+        for j in range(min(stride, n)):
+            pos.append(np.arange(a[h] + j, L[h] + 1, stride))
+            pos_off.append(pos_off[-1] + len(pos[-1]))
+        row_off.append(len(pos_off) - 1)
+    return (np.asarray(row_off, np.int32), np.asarray(pos_off, np.int32),
+            np.concatenate(pos).astype(np.int32) if pos else np.zeros(0, np.int32))
+
+
 def with_context(tokens, hyp_off, utt_off, ctx_tokens, ctx_off, max_len: int = 512, word_start=None,
                  ctx_word_start=None):
     """Sentence pairs ``[CLS] ctx_u [SEP] w_1..w_L [SEP]`` for every hypothesis of utterance u: the

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .data import NBest, PLL_VARIANTS, pll_spans
+from .data import NBest, PLL_VARIANTS, pll_spans, pll_strided
 from .weights import BertShape, BERT_BASE
 
 
@@ -165,11 +165,14 @@ class PLLScorer(BertEngine):
         super().__init__(weights, shape, _lib.RS_HEAD_MLM, device, max_rows, precision)
 
     def score_nbest(self, tokens, hyp_off, return_rows: bool = False, variant: str = "original", word_start=None,
-                    token_types=None, score_from=None):
+                    token_types=None, score_from=None, stride: int = 0):
         """tokens int32 [sum T] ([CLS] w.. [SEP] per hypothesis), hyp_off int [H+1].
 
         ``variant``: "original" (``rs_pll_score``), or "word_l2r" / "whole_word" (``data.pll_spans``
-        over ``word_start``, uint8 per token, through ``score_spans``).
+        over ``word_start``, uint8 per token, through ``score_spans``), or "strided" (``data.pll_strided``
+        with ``stride`` >= 1 through ``score_sets``: every ``stride``-th token masked in one copy and all
+        of them scored from it, ``min(stride, L)`` forwards per hypothesis; an approximation of PLL
+        whose rows come back in ``pll_strided``'s order).
 
         ``token_types``: one segment id per token (``data.with_context``: 0 over ``[CLS] context
         [SEP]``, 1 over the hypothesis).  ``score_from`` int [H]: hypothesis h is scored only at
@@ -177,8 +180,11 @@ class PLLScorer(BertEngine):
         through ``score_spans``.
 
         Returns float64 [H] device tensor of PLL (and float32 per-row log-probs)."""
+        if variant == "strided":
+            return self.score_sets(tokens, hyp_off, *pll_strided(hyp_off, stride, score_from=score_from),
+                                   return_rows=return_rows, token_types=token_types)
         if variant not in PLL_VARIANTS:
-            raise ValueError(f"unknown PLL variant {variant!r} {PLL_VARIANTS}")
+            raise ValueError(f"unknown PLL variant {variant!r} {PLL_VARIANTS + ('strided',)}")
         if variant != "original" or score_from is not None:
             if variant != "original" and word_start is None:
                 raise ValueError(f"variant {variant!r} needs word_start")
@@ -217,9 +223,68 @@ class PLLScorer(BertEngine):
                                                _lib.stream_ptr(self.device)))
         return (pll, rows) if return_rows else pll
 
+    def score_sets(self, tokens, hyp_off, row_off, pos_off, pos, return_rows: bool = False, token_types=None):
+        """Multi-mask PLL rows (``rs_pll_score_sets``): row r of hypothesis h (``row_off[h] <= r <
+        row_off[h + 1]``) is the hypothesis with every position of ``pos[pos_off[r]:pos_off[r + 1]]``
+        replaced by [MASK], and every one of them is scored from that one forward (positions relative
+        to the hypothesis, strictly ascending within a row, ``1 <= p <= T - 2``, at least one per row).
+
+        Returns float64 [H] device tensor (sum of each hypothesis' entries in list order; no rows: 0)
+        and, with ``return_rows``, the float32 log-prob of every entry of ``pos``."""
+        d_tok, off, n_hyp = self._hyps(tokens, hyp_off)
+        roff = np.ascontiguousarray(row_off, np.int32)
+        if len(roff) != n_hyp + 1:
+            raise ValueError("row_off must have one entry per hypothesis plus one")
+        n_rows = max(int(roff[-1]), 0) if n_hyp else 0
+        poff = np.ascontiguousarray(pos_off, np.int32)
+        ps = np.ascontiguousarray(pos, np.int32)
+        if len(poff) != n_rows + 1:
+            raise ValueError("pos_off must have row_off[-1] + 1 entries")
+        n_pos = max(int(poff[-1]), 0)
+        if len(ps) != n_pos:
+            raise ValueError("pos must have pos_off[-1] entries")
+        pll = torch.empty(n_hyp, dtype=torch.float64, device=self.device)
+        rows = torch.empty(n_pos, dtype=torch.float32, device=self.device) if return_rows else None
+        d_type = self._set_types(token_types)      # noqa: F841
+        _lib.check(self.lib.rs_pll_score_sets(self.handle, _lib.ptr(d_tok), off.ctypes.data, n_hyp, roff.ctypes.data,
+                                              poff.ctypes.data, ps.ctypes.data, _lib.ptr(pll), _lib.ptr(rows),
+                                              _lib.stream_ptr(self.device)))
+        return (pll, rows) if return_rows else pll
+
     def score(self, nb: NBest) -> np.ndarray:
         return self.score_nbest(nb.tokens, nb.hyp_off, token_types=nb.token_type,
                                 score_from=nb.score_from).cpu().numpy()
+
+    def masked_logprob_multi(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, labels: torch.Tensor,
+                             token_type_ids=None) -> torch.Tensor:
+        """``BertForMaskedLM(input_ids, labels)`` per-position log-probs for a padded batch [B, T] whose
+        rows are already masked: every position with ``labels != -100`` (any number >= 1 per row, inside
+        the row's attended prefix) is scored against its label from the row's one forward
+        (``rs_masked_logprob_multi``).  Returns float32 [B, T] on the device,
+        ``log_softmax(logits[b, t])[labels[b, t]]`` at the scored positions and ``nan`` elsewhere
+        (their mean, negated, is the model's loss)."""
+        d_ids, off, types = _ragged(input_ids, attention_mask, token_type_ids, self.device)
+        B, T = input_ids.shape
+        lab = labels.to(self.device)
+        if lab.shape != input_ids.shape:
+            raise ValueError("labels must have the shape of input_ids")
+        lens = torch.from_numpy(np.diff(off).astype(np.int64)).to(self.device)
+        scored = lab != -100
+        if bool((scored & (torch.arange(T, device=self.device)[None, :] >= lens[:, None])).any()):
+            raise ValueError("a label outside its row's attended prefix")
+        b_idx, t_idx = torch.nonzero(scored, as_tuple=True)          # row-major: ascending within a row
+        q_off = np.zeros(B + 1, np.int32)
+        q_off[1:] = np.cumsum(scored.sum(1).cpu().numpy())
+        qpos = t_idx.to(torch.int32).cpu().numpy()
+        d_lab = lab[b_idx, t_idx].to(torch.int32).contiguous()
+        out = torch.empty(len(qpos), dtype=torch.float32, device=self.device)
+        d_type = self._set_types(types)      # noqa: F841
+        _lib.check(self.lib.rs_masked_logprob_multi(self.handle, _lib.ptr(d_ids), off.ctypes.data, B, q_off.ctypes.data,
+                                                    _lib.ptr(qpos), _lib.ptr(d_lab), _lib.ptr(out),
+                                                    _lib.stream_ptr(self.device)))
+        full = torch.full((B, T), float("nan"), dtype=torch.float32, device=self.device)
+        full[b_idx, t_idx] = out
+        return full
 
     def masked_logprob(self, input_ids: torch.Tensor, attention_mask: torch.Tensor,
                        labels: torch.Tensor, mask_pos, token_type_ids=None) -> torch.Tensor:

@@ -195,6 +195,44 @@ int rs_masked_logprob(rs_model* m, const int32_t* d_ids, const int32_t* h_seq_of
                       const int32_t* h_query, const int32_t* d_label, int32_t n_seq,
                       float* d_out, void* stream);
 
+/* Multi-mask rows: several [MASK] positions in one row, every one of them scored from that row's
+ * single forward.  Reference seam: BertForMaskedLM(input_ids, labels) with labels at every masked
+ * position and -100 elsewhere (MLM_PLL/main.py:89-97 passes labels for all positions); the strided
+ * PLL approximation masks every k-th token of one copy and scores all of them from it, min(k, L)
+ * forwards per hypothesis instead of L.
+ *   h_row_off  int32 [n_hyp + 1] host   rows (forwards) of hypothesis h: [h_row_off[h], h_row_off[h+1]);
+ *                                       ascending, h_row_off[0] == 0
+ *   h_pos_off  int32 [n_rows + 1] host  positions of row r: h_pos[h_pos_off[r] .. h_pos_off[r+1])
+ *   h_pos      int32 [n_pos] host       relative to the hypothesis, strictly ascending within a row,
+ *                                       1 <= p <= T - 2, at least one per row; anything else RS_EARG
+ *                                       with a message naming the row
+ *   d_pos_lp   float32 [n_pos] or NULL: log_softmax(logits[pos_i])[tok[pos_i]] of the row that holds
+ *                                       position i, that row being the hypothesis with all of ITS
+ *                                       positions replaced by [MASK] on the device
+ *   d_pll      float64 [n_hyp]: the sum of the hypothesis' entries in list order; no rows: 0.0
+ * One position per row, p = 1..L, is rs_pll_score's row list.  A position's value does not depend on
+ * which of its row's other [MASK] positions are scored, and results are bitwise reproducible.
+ * The last layer and the head run one state row per POSITION; a launch chunk holds at most
+ * max_rows / 3 + 1 of them (the per-sequence workspace of the other calls), so a single row with
+ * more positions than that is RS_EARG (the message names the max_rows that fits it).
+ * Layer-0 dedup does not apply: these calls run layer 0 over all token rows (the dedup is exact, so
+ * no score depends on it).  No top-k form.  Precision modes, chunking, rs_model_set_token_types,
+ * the last-layer query path, the range guard, deferred checks and call ordering are those of
+ * rs_pll_score.  A model without the MLM head: RS_ESTATE; with fewer than 2 layers: RS_EUNSUP. */
+int rs_pll_score_sets(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off, int32_t n_hyp,
+                      const int32_t* h_row_off, const int32_t* h_pos_off, const int32_t* h_pos,
+                      double* d_pll, float* d_pos_lp, void* stream);
+/* rs_masked_logprob with any number (>= 1) of query positions per row; the rows are already masked by
+ * the caller.
+ *   h_q_off    int32 [n_seq + 1] host   queries of row s: h_qpos[h_q_off[s] .. h_q_off[s+1])
+ *   h_qpos     int32 [n_q] host         strictly ascending within a row, 0 <= p < T (else RS_EARG)
+ *   d_label    int32 [n_q]              label id per query; -1 = the token id at the position
+ *   d_out      float32 [n_q]            log_softmax(logits[qpos_i])[label_i]
+ * A label outside [0, vocab) has log-probability -inf: RS_EUNSUP through the range guard. */
+int rs_masked_logprob_multi(rs_model* m, const int32_t* d_ids, const int32_t* h_seq_off, int32_t n_seq,
+                            const int32_t* h_q_off, const int32_t* h_qpos, const int32_t* d_label,
+                            float* d_out, void* stream);
+
 /* Top-k token candidates at masked positions: the model's k preferred vocabulary entries of a row
  * and their log-probabilities.  Reference seam: logits[range(B), mask_pos] of MLM_PLL/main.py:101-105
  * BEFORE the label gather — the reference forms the whole [B, vocab] row and keeps one entry; these
