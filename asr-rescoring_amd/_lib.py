@@ -83,6 +83,7 @@ _SIGS = {
     "rs_trainer_finalize": (ctypes.c_int, [P]),
     "rs_train_step_cls": (ctypes.c_int, [P, P, P, I32, P, I32, P, P, P, ctypes.POINTER(RsTrainOpts), P, P, P]),
     "rs_train_step_mlm": (ctypes.c_int, [P, P, P, I32, P, P, ctypes.POINTER(RsTrainOpts), P, P]),
+    "rs_train_step_mlm_labeled": (ctypes.c_int, [P, P, P, I32, P, P, I32, P, ctypes.POINTER(RsTrainOpts), P, P]),
     "rs_trainer_get_tensor": (ctypes.c_int, [P, ctypes.c_char_p, P, I64]),
     "rs_trainer_get_grad": (ctypes.c_int, [P, ctypes.c_char_p, P, I64]),
     "rs_trainer_reset_optimizer": (ctypes.c_int, [P]),

@@ -18,7 +18,9 @@ names a ``vocab.txt`` — then the native BertTokenizer-compatible ``frontend.Na
 ``mode`` (rescore fusion formula: norm / legacy / am_norm), ``pll_variant`` (mlm_pll: original / word_l2r / whole_word), ``pll_stride`` (mlm_pll: strided PLL approximation),
 ``{split}_context_text_path`` (mlm_pll, mlm_topk, rescorebert, rescorebert_train: JSON ``{utt_id: text}``; every
 hypothesis of the utterance becomes the pair ``[CLS] context [SEP] hypothesis [SEP]`` with segment ids 0 / 1,
-``data.with_context``; a missing utterance has no context; MLM scores cover the hypothesis half only).
+``data.with_context``; a missing utterance has no context; MLM scores cover the hypothesis half only),
+``mlm_labels`` / ``mlm_masking`` / ``mlm_probability`` / ``mlm_whole_word`` (mlm_finetune: labels at the masked
+positions only, dynamic 80/10/10 masking).
 """
 from __future__ import annotations
 
@@ -305,11 +307,31 @@ def mlm_finetune(cfg) -> Dict[str, object]:
     ``random_init_seed`` (initial weights: bert-base-chinese cannot be fetched offline),
     ``train_ref_text_path`` ({utt: text}, expanded by ``do_job_rows``), ``weight_decay``,
     dropout keys (``_dropout_args``).  ``dataloader.shuffle: True`` draws the order from torch.randperm seeded by ``seed`` (not the
-    reference's sampler stream)."""
+    reference's sampler stream).
+    Labels: ``mlm_labels: all`` (default, the reference: a label at every position, pads included) or
+    ``masked`` (each do_job row labelled at its [MASK] only, -100 elsewhere: the head runs on one row
+    per sequence, ``rs_train_step_mlm_labeled``).  ``mlm_masking: do_job`` (default) or ``dynamic``
+    (labelled steps always; ``mlm_labels`` is then refused):
+    one row per sentence (the label row of each run of do_job rows, which must be in order), masked anew every epoch by
+    ``train.mask_tokens`` (BERT's 80/10/10 at ``mlm_probability``, default 0.15) seeded by
+    ``(seed, epoch)`` and the batch index; the dev loss uses the masks of ``(seed, 0)`` at every
+    epoch, so epochs compare; ``mlm_whole_word: true`` selects whole words and needs ``model.vocab``.
+    Checkpoints and ``loss.json`` are the same in every mode."""
     import torch
-    from .train import MLMTrainer, do_job_rows, mlm_epoch
+    from .train import MLMTrainer, do_job_rows, mlm_epoch, mlm_epoch_dynamic
     os.makedirs(cfg.output_path, exist_ok=True)
     n_data = int(get(cfg, "num_of_data", 1 << 62))
+    lab_mode, masking = str(get(cfg, "mlm_labels", "all")), str(get(cfg, "mlm_masking", "do_job"))
+    if lab_mode not in ("all", "masked") or masking not in ("do_job", "dynamic"):
+        raise ValueError("mlm_labels is all or masked, mlm_masking is do_job or dynamic")
+    if masking == "dynamic" and get(cfg, "mlm_labels") is not None:
+        raise ValueError("mlm_labels applies to mlm_masking: do_job only (dynamic masking always labels the "
+                         "selected positions alone)")
+    prob = float(get(cfg, "mlm_probability", 0.15))
+    whole_word = bool(get(cfg, "mlm_whole_word", False))
+    vocab_path = get(cfg, "model.vocab")
+    if whole_word and (masking != "dynamic" or not (vocab_path and os.path.exists(vocab_path))):
+        raise ValueError("mlm_whole_word needs mlm_masking: dynamic and model.vocab")
 
     def rows_of(split):
         rows_path, ref_path = get(cfg, f"{split}_data_path"), get(cfg, f"{split}_ref_text_path")
@@ -327,6 +349,50 @@ def mlm_finetune(cfg) -> Dict[str, object]:
     train_d, dev_d = rows_of("train"), rows_of("dev")
     if train_d is None:
         raise FileNotFoundError("train_data_path (do_job rows) or train_ref_text_path is required")
+
+    def masked_only(d):
+        """do_job rows labelled at their [MASK] only: the position where ids and labels differ
+        (a row whose masked token is [MASK] itself: its first [MASK])."""
+        out = []
+        for ids, lab in zip(*d):
+            diff = [p for p, (a, b) in enumerate(zip(ids, lab)) if a != b]
+            p = diff[0] if diff else list(ids).index(D.MASK_ID)
+            out.append([-100] * p + [lab[p]] + [-100] * (len(lab) - p - 1))
+        return d[0], out
+
+    def sentences_of(d):
+        """The sentences behind do_job rows (a sentence of n words gives n consecutive rows with
+        the sentence as labels; ``num_of_data`` may cut the last sentence's rows short), and their
+        ``##`` continuation flags for whole-word masking.  Rows that are not such runs — reordered,
+        or a sentence's rows incomplete before the end — raise ``ValueError``."""
+        sents, i = [], 0
+        while i < len(d[1]):
+            h = list(d[1][i])
+            n = max(len(h) - 2, 1)
+            for j in range(i + 1, min(i + n, len(d[1]))):
+                if list(d[1][j]) != h:
+                    raise ValueError(f"mlm_masking: dynamic needs do_job rows in order: row {j} does not carry the "
+                                     f"labels of row {i}, whose sentence has {n} rows")
+            sents.append(h)
+            i += n
+        cont = None
+        if whole_word:
+            from .frontend import NativeTokenizer
+            tok = NativeTokenizer(vocab_path)
+            cont = [(1 - tok.word_starts(s)).tolist() for s in sents]
+        return sents, cont
+    if masking == "dynamic":
+        train_d, dev_d = sentences_of(train_d), None if dev_d is None else sentences_of(dev_d)
+    elif lab_mode == "masked":
+        train_d, dev_d = masked_only(train_d), None if dev_d is None else masked_only(dev_d)
+    ignore = -100 if lab_mode == "masked" else None
+    seed = int(get(cfg, "seed", 0))
+
+    def epoch_pass(d, ep, update, order=None):
+        if masking == "dynamic":
+            return mlm_epoch_dynamic(tr, d[0], bs, (seed, ep), update=update, order=order, mlm_probability=prob,
+                                     continuation=d[1])
+        return mlm_epoch(tr, *d, bs, update=update, order=order, ignore_index=ignore)
     tr = MLMTrainer(_weights(cfg, "mlm"), BERT_BASE, device=_dev(cfg), lr=float(get(cfg, "lr", 1e-5)),
                     weight_decay=float(get(cfg, "weight_decay", 0.01)), **_dropout_args(cfg))
     bs = int(get(cfg, "dataloader.batch_size", get(cfg, "batch_size", 32)))
@@ -339,10 +405,10 @@ def mlm_finetune(cfg) -> Dict[str, object]:
             tr.reset_optimizer()
             tr.set_dropout_step(ep << 32)            # epoch-keyed masks: a resumed run draws the same
             order = torch.randperm(len(train_d[0]), generator=gen).numpy() if shuffle else None
-            train_rec[ep - 1] = mlm_epoch(tr, *train_d, bs, update=True, order=order)
+            train_rec[ep - 1] = epoch_pass(train_d, ep, True, order)
             print("epoch ", ep, " train loss: ", train_rec[ep - 1])
             if dev_d is not None:
-                dev_rec[ep - 1] = mlm_epoch(tr, *dev_d, bs, update="loss")
+                dev_rec[ep - 1] = epoch_pass(dev_d, 0, "loss")
                 print("epoch ", ep, " dev loss: ", dev_rec[ep - 1], "\n")
             ckpts.append(_save_checkpoint(cfg.output_path, tr.state_dict(), ep))
             D.json_saving(os.path.join(cfg.output_path, "loss.json"), {"train": train_rec, "dev": dev_rec})

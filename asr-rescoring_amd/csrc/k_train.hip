@@ -958,6 +958,32 @@ __global__ void tr_dropout_keep_kernel(uint8_t* __restrict__ keep, long long n, 
         keep[i] = dr.thresh == 0 ? 1 : (uint8_t)tr_keep(dr, (unsigned long long)i);
 }
 
+// Labelled-row MLM head (rs_train_step_mlm_labeled): rows of H floats moved as float4 quads (h4 = H / 4
+// per row), a flat grid-stride over the quads of the written side, so consecutive lanes move
+// consecutive 16 B of one row and every quad of dst has exactly one writer.
+// dst[k] = src[rows[k]], k < n (rows validated by the host: in [0, M))
+__global__ void __launch_bounds__(256)
+tr_gather_rows_kernel(const float4* __restrict__ src, const int* __restrict__ rows, long long n4, int h4,
+                      float4* __restrict__ dst) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+        const long long k = i / h4;
+        const int c = (int)(i - k * h4);
+        dst[i] = src[(long long)rows[k] * h4 + c];
+    }
+}
+
+// dst[r] = inv[r] >= 0 ? src[inv[r]] : 0, r < M: the whole of dst in one pass (no memset + scatter)
+__global__ void __launch_bounds__(256)
+tr_expand_rows_kernel(const float4* __restrict__ src, const int* __restrict__ inv, long long m4, int h4,
+                      float4* __restrict__ dst) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < m4; i += (long long)gridDim.x * blockDim.x) {
+        const long long r = i / h4;
+        const int c = (int)(i - r * h4);
+        const int k = inv[r];
+        dst[i] = k >= 0 ? src[(long long)k * h4 + c] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+
 int grid_for(long long n, int bs) { return (int)std::min<long long>((n + bs - 1) / bs, 8192); }
 
 }  // namespace
@@ -1236,6 +1262,24 @@ hipError_t tr_adamw(float* p, const float* g, float* m, float* v, long long n, f
 hipError_t tr_dropout(float* dst, const float* src, long long n, const TrDrop& d, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(tr_dropout_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, dst, src, n, d);
+    return hipGetLastError();
+}
+
+hipError_t tr_gather_rows(const float* src, const int* rows, int n, int H, float* dst, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    if (H <= 0 || H % 4 || ((uintptr_t)src | (uintptr_t)dst) % 16) return hipErrorInvalidValue;
+    const long long n4 = (long long)n * (H / 4);
+    hipLaunchKernelGGL(tr_gather_rows_kernel, dim3(grid_for(n4, 256)), dim3(256), 0, s, (const float4*)src, rows, n4,
+                       H / 4, (float4*)dst);
+    return hipGetLastError();
+}
+
+hipError_t tr_expand_rows(const float* src, const int* inv, int M, int H, float* dst, hipStream_t s) {
+    if (M <= 0) return hipSuccess;
+    if (H <= 0 || H % 4 || ((uintptr_t)src | (uintptr_t)dst) % 16) return hipErrorInvalidValue;
+    const long long m4 = (long long)M * (H / 4);
+    hipLaunchKernelGGL(tr_expand_rows_kernel, dim3(grid_for(m4, 256)), dim3(256), 0, s, (const float4*)src, inv, m4,
+                       H / 4, (float4*)dst);
     return hipGetLastError();
 }
 

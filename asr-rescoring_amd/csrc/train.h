@@ -105,6 +105,11 @@ hipError_t tr_cls_bwd(const float* dsc, const float* h, const int* seq_off, int 
 hipError_t tr_loss(const float* sc, const float* tgt, const float* am, const float* err, const int* utt_off,
                    int n_utt, int n_hyp, int kind, float md_w, float* dsc, float* uloss, float* loss, hipStream_t s);
 hipError_t tr_ce(float* logits, const int* labels, int M, int V, float* row_loss, float* loss, hipStream_t s);
+// Labelled-row MLM head: dst [n, H] = the rows src[rows[k]] of src [M, H] (rows: device, in [0, M));
+// dst [M, H] = src[inv[r]] where inv[r] >= 0, zeros elsewhere (inv: device, [M], the inverse of rows).
+// H % 4 == 0, 16-B aligned rows; every element of dst has one writer (geometry-independent).
+hipError_t tr_gather_rows(const float* src, const int* rows, int n, int H, float* dst, hipStream_t s);
+hipError_t tr_expand_rows(const float* src, const int* inv, int M, int H, float* dst, hipStream_t s);
 hipError_t tr_adamw(float* p, const float* g, float* m, float* v, long long n, float decay, float b1w, float b2,
                     float b2w, float step_size, float bc2_sqrt, float eps, hipStream_t s);
 // fp32 GEMM on the f32-input MFMA (k_sgemm.hip): C[M][N] = A·B (+ C when accum), A read as

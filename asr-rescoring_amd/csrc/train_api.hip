@@ -290,6 +290,10 @@ struct StepCtx {
     const int* seq = nullptr;
     size_t i_tok = 0, i_pos = 0, i_aux = 0, i_utok = 0, i_toff = 0, i_ord = 0, i_klen = 0;
     size_t i_type = 0;              // row types column (0: the step has no segment ids)
+    // labelled-row MLM head (rs_train_step_mlm_labeled): R head rows, their row indices and the
+    // inverse map (row -> compact index, -1: unlabelled) as metadata columns; R == M without
+    int R = 0;
+    size_t i_lrow = 0, i_linv = 0;
     const int* row_type() const { return i_type ? dm + i_type : nullptr; }
     float* x0 = nullptr;
     float2* st0 = nullptr;
@@ -300,6 +304,7 @@ struct StepCtx {
     float* dS = nullptr;            // tiled backward: dS of one layer, the saved-P layout
     // MLM head (RS_HEAD_MLM): transform pre-GELU / GELU out (pre-LN) / LN out, stats, logits
     float *tpre = nullptr, *tx = nullptr, *th = nullptr, *logits = nullptr;
+    float* hc = nullptr;            // labelled rows of the final hidden state, compact [R, H]
     float2* tst = nullptr;
     // dropout of this step (train mode: update >= 0 and p > 0)
     uint32_t seed = 0, th_hidden = 0, th_attn = 0;
@@ -350,8 +355,14 @@ int set_dropout(StepCtx& c, const rs_train_opts* o) {
 // host metadata + buffers.  aux: extra int32 array uploaded with the metadata (utt_off);
 // h_klen (nullable): per-sequence key lengths (padded-batch rows, rs_train_step_mlm).
 // ty: the step's segment ids (d_type null: none), one per token row.
+// h_lab (nullable): the n_lab token rows the MLM head runs on, strictly ascending in [0, M) (checked
+// by rs_train_step_mlm_labeled before any trainer state moves, and again here, next to the offsets
+// that define M, before anything is sized or uploaded from the list); the head
+// regions are then sized by n_lab and one more holds the gathered hidden rows.  Without it the head
+// has all M rows and the layout is the one rs_train_step_mlm always had.
 int prepare(StepCtx& c, const TypeStep& ty, const int32_t* d_tok, const int32_t* h_off, int n_seq,
-            const std::vector<int>& aux, const int32_t* h_klen = nullptr) {
+            const std::vector<int>& aux, const int32_t* h_klen = nullptr, const int32_t* h_lab = nullptr,
+            int n_lab = 0) {
     rs_trainer* t = c.t;
     const rs_bert_cfg& cf = t->cfg;
     const int H = cf.hidden, F = cf.intermediate, nh = cf.heads, NL = cf.layers;
@@ -377,6 +388,16 @@ int prepare(StepCtx& c, const TypeStep& ty, const int32_t* d_tok, const int32_t*
             if (h_klen[s] < 1 || h_klen[s] > h_off[s + 1] - h_off[s])
                 return rs_fail(RS_EARG, "key length outside 1..row length");
     const int M = c.M, S = c.S;
+    c.R = h_lab ? n_lab : M;
+    for (int k = 0; k < (h_lab ? n_lab : 0); ++k) {
+        if (h_lab[k] < 0 || h_lab[k] >= M)
+            return rs_fail(RS_EARG, "h_lab_row[" + std::to_string(k) + "] = " + std::to_string(h_lab[k]) +
+                                        " is outside the batch's " + std::to_string(M) + " token rows");
+        if (k && h_lab[k] <= h_lab[k - 1])
+            return rs_fail(RS_EARG, "h_lab_row[" + std::to_string(k) + "] = " + std::to_string(h_lab[k]) +
+                                        " is not above h_lab_row[" + std::to_string(k - 1) + "] = " +
+                                        std::to_string(h_lab[k - 1]) + " (strictly ascending rows)");
+    }
     hipStream_t st = c.st;
     TRY_HIP(hipSetDevice(t->device));
     TRY_BLAS(rocblas_set_stream(t->blas, st));
@@ -408,6 +429,7 @@ int prepare(StepCtx& c, const TypeStep& ty, const int32_t* d_tok, const int32_t*
         pofs[s + 1] = pofs[s] + (long long)nh * T * T;
     }
     // int layout: pofs (int64) | row_tok | row_pos | seq_off | aux | utok | toff | order | klen | row_type
+    //             | lab_row | lab_inv
     std::vector<int>& hm = t->h_meta;
     hm.assign(2 * (S + 1), 0);
     std::memcpy(hm.data(), pofs.data(), (S + 1) * 8);
@@ -435,6 +457,14 @@ int prepare(StepCtx& c, const TypeStep& ty, const int32_t* d_tok, const int32_t*
         c.i_type = hm.size();
         hm.insert(hm.end(), t->h_type.begin(), t->h_type.end());
     }
+    c.i_lrow = c.i_linv = 0;
+    if (h_lab) {
+        c.i_lrow = hm.size();
+        hm.insert(hm.end(), h_lab, h_lab + n_lab);
+        c.i_linv = hm.size();
+        hm.insert(hm.end(), (size_t)M, -1);
+        for (int k = 0; k < n_lab; ++k) hm[c.i_linv + h_lab[k]] = k;
+    }
     TRY_ALLOC(t->meta.ensure(hm.size() * 4));
     TRY_HIP(hipMemcpyAsync(t->meta.p, hm.data(), hm.size() * 4, hipMemcpyHostToDevice, st));
     c.dm = (const int*)t->meta.p;
@@ -447,17 +477,22 @@ int prepare(StepCtx& c, const TypeStep& ty, const int32_t* d_tok, const int32_t*
     auto al = [](size_t n) { return (n + 63) & ~(size_t)63; };
     const size_t MH = al((size_t)M * H), MF = al((size_t)M * F), M2 = al((size_t)M * 2), PS = al((size_t)pofs[S]);
     const size_t QKV = al((size_t)M * 3 * H);
-    const size_t MV = mlm ? al((size_t)M * cf.vocab) : 0;
+    // the MLM head's regions by its own row count R (R == M: the sizes they always had)
+    const int R = c.R;
+    const size_t RH = al((size_t)R * H), R2 = al((size_t)R * 2), RV = mlm ? al((size_t)R * cf.vocab) : 0;
     const size_t per_layer = MH + QKV + PS + MH + MH + M2 + MH + 2 * MF + MH + M2;
-    const size_t n_head = mlm ? 3 * MH + M2 + MV : 0;
+    const size_t n_head = mlm ? 3 * RH + R2 + RV + (h_lab ? RH : 0) : 0;
     const size_t n_act = MH + M2 + NL * per_layer + MH + n_head;
     TRY_ALLOC(t->act.ensure(n_act * 4));
     const int widest = std::max(std::max(3 * H, F), mlm ? cf.vocab : 0);
-    const size_t n_part = al(tr_colsum_scratch(M, widest) / 4);
+    const size_t n_part = al(tr_colsum_scratch(M, widest) / 4);   // grows with the rows: covers the head's R <= M
     const size_t n_tail = al(2 * (size_t)S + aux.size() + M + 64);
     const size_t n_grad = 2 * MH + QKV + MF + n_part + n_tail + (c.tiled ? PS : 0);
     TRY_ALLOC(t->grad.ensure(n_grad * 4));
-    TRY_ALLOC(t->ws.ensure(std::max<size_t>(sgemm_ws_floats(cf, M), 64) * 4));
+    // the picker may split K differently at the head's R rows: its (R, V, H) shapes sized too
+    size_t n_ws = sgemm_ws_floats(cf, M);
+    if (R != M) n_ws = std::max(n_ws, sgemm_ws_floats(cf, R));
+    TRY_ALLOC(t->ws.ensure(std::max<size_t>(n_ws, 64) * 4));
     float* A = t->act.as<float>();
     c.x0 = A;
     c.st0 = (float2*)(c.x0 + MH);
@@ -481,10 +516,11 @@ int prepare(StepCtx& c, const TypeStep& ty, const int32_t* d_tok, const int32_t*
     }
     if (mlm) {
         c.tpre = c.la[NL].hin + MH;
-        c.tx = c.tpre + MH;
-        c.th = c.tx + MH;
-        c.tst = (float2*)(c.th + MH);
-        c.logits = c.th + MH + M2;
+        c.tx = c.tpre + RH;
+        c.th = c.tx + RH;
+        c.tst = (float2*)(c.th + RH);
+        c.logits = c.th + RH + R2;
+        c.hc = h_lab ? c.logits + RV : nullptr;
     }
     float* G = t->grad.as<float>();
     c.dA = G;
@@ -659,6 +695,65 @@ int rs_train_step_cls(rs_trainer* t, const int32_t* d_tok, const int32_t* h_hyp_
     return RS_OK;
 }
 
+// The MLM step behind both entries.  h_lab null: the head over all M rows (rs_train_step_mlm, one
+// label per row).  Otherwise over the n_lab rows h_lab names: their final hidden rows gathered into
+// c.hc, the same head sequence on n_lab rows (CE mean over n_lab), and the head's gradient w.r.t.
+// the hidden state expanded back to [M, H] with zeros at the unlabelled rows.
+static int mlm_step(rs_trainer* t, const TypeStep& ty, const int32_t* d_ids, const int32_t* h_seq_off, int32_t n_seq,
+                    const int32_t* h_key_len, const int32_t* h_lab, int32_t n_lab, const int32_t* d_labels,
+                    const rs_train_opts* o, float* d_loss, void* stream) {
+    StepCtx c;
+    c.t = t;
+    c.st = (hipStream_t)stream;
+    if (int r = set_dropout(c, o)) return r;
+    if (int r = prepare(c, ty, d_ids, h_seq_off, n_seq, {}, h_key_len, h_lab, n_lab)) return r;
+    if (int r = encoder_forward(c)) return r;
+    const rs_bert_cfg& cf = t->cfg;
+    const int H = cf.hidden, V = cf.vocab, M = c.M, R = c.R;
+    float *Pm = t->P.as<float>(), *Gm = t->G.as<float>();
+    hipStream_t st = c.st;
+    const float* hfin = c.la[cf.layers].hin;
+    if (h_lab) {
+        TRY_HIP(tr_gather_rows(hfin, c.dm + c.i_lrow, R, H, c.hc, st));
+        hfin = c.hc;
+    }
+    // BertOnlyMLMHead: transform (dense + GELU + LN), tied decoder + bias (modeling_bert.py:466-506)
+    RS_TRY(gemm_nt(t, st, R, H, H, hfin, Pm + t->o_wt, c.tpre, 0.f));
+    TRY_HIP(tr_bias_gelu(c.tpre, Pm + t->o_bt, c.tx, R, H, st));
+    TRY_HIP(tr_bias_res_ln(c.tx, nullptr, nullptr, R, Pm + t->o_tg, Pm + t->o_tb, cf.ln_eps, H, c.tst, c.th, st));
+    RS_TRY(gemm_nt(t, st, R, V, H, c.th, Pm + t->o_word, c.logits, 0.f));
+    TRY_HIP(tr_bias(c.logits, Pm + t->o_db, R, V, st));
+    float* rl = c.tail;
+    TRY_HIP(tr_ce(c.logits, d_labels, R, V, rl, d_loss, st));       // logits <- dlogits
+    if (o->update < 0) {                      // loss only (the reference's dev pass)
+        TRY_HIP(hipStreamSynchronize(st));
+        return RS_OK;
+    }
+    TRY_HIP(hipMemsetAsync(Gm, 0, t->n_params * 4, st));
+    float* dT = c.dB;
+    float* dT2 = c.dF;
+    TRY_HIP(tr_colsum(c.logits, nullptr, nullptr, R, V, 0, c.part, Gm + t->o_db, 0, st));
+    RS_TRY(gemm_tn(t, st, R, V, H, c.logits, c.th, Gm + t->o_word, 0.f));          // tied decoder part
+    RS_TRY(gemm_nn(t, st, R, V, H, c.logits, Pm + t->o_word, dT, 0.f));
+    TRY_HIP(tr_colsum_ln(dT, c.tx, c.tst, R, H, c.part, Gm + t->o_tg, Gm + t->o_tb, st));
+    TRY_HIP(tr_ln_bwd(dT, c.tx, c.tst, Pm + t->o_tg, dT2, R, H, st));
+    TRY_HIP(tr_gelu_bwd(dT2, c.tpre, (long long)R * H, st));
+    TRY_HIP(tr_colsum(dT2, nullptr, nullptr, R, H, 0, c.part, Gm + t->o_bt, 0, st));
+    RS_TRY(gemm_tn(t, st, R, H, H, dT2, hfin, Gm + t->o_wt, 0.f));
+    if (h_lab) {
+        // d hidden of the labelled rows into dT (free since tr_ln_bwd), then every row of dA
+        RS_TRY(gemm_nn(t, st, R, H, H, dT2, Pm + t->o_wt, dT, 0.f));
+        TRY_HIP(tr_expand_rows(dT, c.dm + c.i_linv, M, H, c.dA, st));
+    } else {
+        RS_TRY(gemm_nn(t, st, M, H, H, dT2, Pm + t->o_wt, c.dA, 0.f));              // dA = d hidden
+    }
+    if (int r = encoder_backward(c)) return r;
+    if (int r = adamw(t, o, st)) return r;
+    TRY_HIP(hipStreamSynchronize(st));
+    if (tr_sgemm_failed()) return rs_fail(RS_EHIP, "a stream-K GEMM timed out waiting for a partial tile");
+    return RS_OK;
+}
+
 int rs_train_step_mlm(rs_trainer* t, const int32_t* d_ids, const int32_t* h_seq_off, int32_t n_seq,
                       const int32_t* h_key_len, const int32_t* d_labels, const rs_train_opts* o, float* d_loss,
                       void* stream) {
@@ -667,46 +762,32 @@ int rs_train_step_mlm(rs_trainer* t, const int32_t* d_ids, const int32_t* h_seq_
         return rs_fail(RS_EARG, "null argument / empty batch");
     if (!t->finalized) return rs_fail(RS_ESTATE, "rs_trainer_finalize not called");
     if (t->cfg.heads_mask != RS_HEAD_MLM) return rs_fail(RS_ESTATE, "trainer has no MLM head");
-    StepCtx c;
-    c.t = t;
-    c.st = (hipStream_t)stream;
-    if (int r = set_dropout(c, o)) return r;
-    if (int r = prepare(c, ty, d_ids, h_seq_off, n_seq, {}, h_key_len)) return r;
-    if (int r = encoder_forward(c)) return r;
-    const rs_bert_cfg& cf = t->cfg;
-    const int H = cf.hidden, V = cf.vocab, M = c.M;
-    float *Pm = t->P.as<float>(), *Gm = t->G.as<float>();
-    hipStream_t st = c.st;
-    const float* hfin = c.la[cf.layers].hin;
-    // BertOnlyMLMHead: transform (dense + GELU + LN), tied decoder + bias (modeling_bert.py:466-506)
-    RS_TRY(gemm_nt(t, st, M, H, H, hfin, Pm + t->o_wt, c.tpre, 0.f));
-    TRY_HIP(tr_bias_gelu(c.tpre, Pm + t->o_bt, c.tx, M, H, st));
-    TRY_HIP(tr_bias_res_ln(c.tx, nullptr, nullptr, M, Pm + t->o_tg, Pm + t->o_tb, cf.ln_eps, H, c.tst, c.th, st));
-    RS_TRY(gemm_nt(t, st, M, V, H, c.th, Pm + t->o_word, c.logits, 0.f));
-    TRY_HIP(tr_bias(c.logits, Pm + t->o_db, M, V, st));
-    float* rl = c.tail;
-    TRY_HIP(tr_ce(c.logits, d_labels, M, V, rl, d_loss, st));       // logits <- dlogits
-    if (o->update < 0) {                      // loss only (the reference's dev pass)
-        TRY_HIP(hipStreamSynchronize(st));
-        return RS_OK;
+    return mlm_step(t, ty, d_ids, h_seq_off, n_seq, h_key_len, nullptr, 0, d_labels, o, d_loss, stream);
+}
+
+int rs_train_step_mlm_labeled(rs_trainer* t, const int32_t* d_ids, const int32_t* h_seq_off, int32_t n_seq,
+                              const int32_t* h_key_len, const int32_t* h_lab_row, int32_t n_lab,
+                              const int32_t* d_lab_id, const rs_train_opts* o, float* d_loss, void* stream) {
+    TypeStep ty(t);
+    if (!t || !h_seq_off || !o || !d_loss || n_seq <= 0 || !d_ids)
+        return rs_fail(RS_EARG, "null argument / empty batch");
+    if (!t->finalized) return rs_fail(RS_ESTATE, "rs_trainer_finalize not called");
+    if (t->cfg.heads_mask != RS_HEAD_MLM) return rs_fail(RS_ESTATE, "trainer has no MLM head");
+    if (n_lab <= 0)
+        return rs_fail(RS_EARG, "n_lab = " + std::to_string(n_lab) + ": a labelled step needs at least one labelled row");
+    if (!h_lab_row || !d_lab_id) return rs_fail(RS_EARG, "null label rows / label ids");
+    // the row list against the batch's M rows, before the dropout-step counter or anything else moves
+    const int M = h_seq_off[n_seq];
+    for (int k = 0; k < n_lab; ++k) {
+        if (h_lab_row[k] < 0 || h_lab_row[k] >= M)
+            return rs_fail(RS_EARG, "h_lab_row[" + std::to_string(k) + "] = " + std::to_string(h_lab_row[k]) +
+                                        " is outside the batch's " + std::to_string(M) + " token rows");
+        if (k && h_lab_row[k] <= h_lab_row[k - 1])
+            return rs_fail(RS_EARG, "h_lab_row[" + std::to_string(k) + "] = " + std::to_string(h_lab_row[k]) +
+                                        " is not above h_lab_row[" + std::to_string(k - 1) + "] = " +
+                                        std::to_string(h_lab_row[k - 1]) + " (strictly ascending rows)");
     }
-    TRY_HIP(hipMemsetAsync(Gm, 0, t->n_params * 4, st));
-    float* dT = c.dB;
-    float* dT2 = c.dF;
-    TRY_HIP(tr_colsum(c.logits, nullptr, nullptr, M, V, 0, c.part, Gm + t->o_db, 0, st));
-    RS_TRY(gemm_tn(t, st, M, V, H, c.logits, c.th, Gm + t->o_word, 0.f));          // tied decoder part
-    RS_TRY(gemm_nn(t, st, M, V, H, c.logits, Pm + t->o_word, dT, 0.f));
-    TRY_HIP(tr_colsum_ln(dT, c.tx, c.tst, M, H, c.part, Gm + t->o_tg, Gm + t->o_tb, st));
-    TRY_HIP(tr_ln_bwd(dT, c.tx, c.tst, Pm + t->o_tg, dT2, M, H, st));
-    TRY_HIP(tr_gelu_bwd(dT2, c.tpre, (long long)M * H, st));
-    TRY_HIP(tr_colsum(dT2, nullptr, nullptr, M, H, 0, c.part, Gm + t->o_bt, 0, st));
-    RS_TRY(gemm_tn(t, st, M, H, H, dT2, hfin, Gm + t->o_wt, 0.f));
-    RS_TRY(gemm_nn(t, st, M, H, H, dT2, Pm + t->o_wt, c.dA, 0.f));                  // dA = d hidden
-    if (int r = encoder_backward(c)) return r;
-    if (int r = adamw(t, o, st)) return r;
-    TRY_HIP(hipStreamSynchronize(st));
-    if (tr_sgemm_failed()) return rs_fail(RS_EHIP, "a stream-K GEMM timed out waiting for a partial tile");
-    return RS_OK;
+    return mlm_step(t, ty, d_ids, h_seq_off, n_seq, h_key_len, h_lab_row, n_lab, d_lab_id, o, d_loss, stream);
 }
 
 int rs_trainer_reset_optimizer(rs_trainer* t) {

@@ -27,7 +27,10 @@ itself cannot be matched, so a reference run with dropout is matched in distribu
 ``MLMTrainer`` (BertForMaskedLM, decoder tied to the word embeddings) takes the reference's
 padded batches (``pad_rows``: collate of MLM_PLL/main.py:28-54 — ids and labels padded with
 0, pad positions are queries but not keys) and averages the CE over every position,
-[PAD]-labelled pads included, as BertForMaskedLM's loss does there.
+[PAD]-labelled pads included, as BertForMaskedLM's loss does there.  With ``ignore_index`` (-100,
+the ``BertForMaskedLM(input_ids, labels)`` convention) the CE is the mean over the labelled positions
+and the head runs on those rows only (``rs_train_step_mlm_labeled``); ``mask_tokens`` is the seeded
+80/10/10 dynamic-masking collator that produces such labels.
 """
 from __future__ import annotations
 
@@ -225,15 +228,16 @@ def reference_groups(n_rows: int, n_best: int) -> np.ndarray:
     return np.arange(0, n_rows + 1, n_best, dtype=np.int32)
 
 
-def pad_rows(seqs: Sequence[Sequence[int]], labels: Sequence[Sequence[int]], types=None):
+def pad_rows(seqs: Sequence[Sequence[int]], labels: Sequence[Sequence[int]], types=None, label_pad: int = 0):
     """The reference's MLM batch (collate, MLM_PLL/main.py:28-54): every row padded to the
     batch's longest with id 0 and label 0 (pad_sequence); the attention mask's zeros become
     key lengths.  Returns (ids, row_off, labels, key_len) as int32, and with ``types`` (a segment-id
-    row per sequence) a fifth item, the types padded with 0 like the ids."""
+    row per sequence) a fifth item, the types padded with 0 like the ids.  ``label_pad``: the value
+    that pads the labels (the ``ignore_index`` of a labelled step, so that pads carry no label)."""
     T = max(len(x) for x in seqs)
     n = len(seqs)
     ids = np.zeros((n, T), np.int32)
-    lab = np.zeros((n, T), np.int32)
+    lab = np.full((n, T), label_pad, np.int32)
     klen = np.empty(n, np.int32)
     for i, (x, y) in enumerate(zip(seqs, labels)):
         ids[i, :len(x)] = x
@@ -248,26 +252,60 @@ def pad_rows(seqs: Sequence[Sequence[int]], labels: Sequence[Sequence[int]], typ
     return out + (tt.ravel(),)
 
 
+def labelled_rows(labels, ignore_index: int, vocab: int, n_tok: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The labelled positions of a labels array with one entry per token row (``ignore_index``, the
+    -100 of ``BertForMaskedLM(input_ids, labels)``, marks a position without a label): (row indices,
+    ascending; label ids) as int32, the ``h_lab_row`` / ``d_lab_id`` of ``rs_train_step_mlm_labeled``.
+    ``ValueError`` for a label count other than ``n_tok``, any other label outside ``[0, vocab)``, and
+    no labelled position at all (HF's loss is NaN there)."""
+    lab = np.ascontiguousarray(np.asarray(labels).reshape(-1), np.int32)
+    if len(lab) != n_tok:
+        raise ValueError(f"labels needs one entry per token ({n_tok}), got {len(lab)}")
+    rows = np.flatnonzero(lab != ignore_index).astype(np.int32)
+    if len(rows) == 0:
+        raise ValueError(f"no labelled position: every label is ignore_index ({ignore_index})")
+    ids = np.ascontiguousarray(lab[rows])
+    if ids.min() < 0 or ids.max() >= vocab:
+        bad = int(rows[np.flatnonzero((ids < 0) | (ids >= vocab))[0]])
+        raise ValueError(f"label {int(lab[bad])} at position {bad} is neither ignore_index ({ignore_index}) "
+                         f"nor in [0, {vocab})")
+    return rows, ids
+
+
 class MLMTrainer(_Trainer):
     """MLM fine-tuning (MLM_PLL/main.py:73-161): BertForMaskedLM, CE over every position of the
     (padded) rows, mean; AdamW.  ``key_len`` marks each row's padding (``pad_rows``); without
-    it the rows are ragged and every position is real."""
+    it the rows are ragged and every position is real.  With ``ignore_index`` (normally -100) the
+    labels follow ``BertForMaskedLM(input_ids, labels)``: positions labelled ``ignore_index`` carry no
+    loss, the CE is the mean over the others, and the head (transform + tied decoder) runs on those
+    rows only (``rs_train_step_mlm_labeled``)."""
     HEAD = "mlm"
 
-    def step(self, ids, seq_off, labels, key_len=None, update=True, token_types=None) -> float:
+    def step(self, ids, seq_off, labels, key_len=None, update=True, token_types=None,
+             ignore_index: Optional[int] = None) -> float:
         off = np.ascontiguousarray(seq_off, np.int32)
         kl = None if key_len is None else np.ascontiguousarray(key_len, np.int32)
         if kl is not None and len(kl) != len(off) - 1:
             raise ValueError("key_len needs one entry per row")
         dev = self.device
+        rows = None
+        if ignore_index is not None:
+            rows, labels = labelled_rows(labels, int(ignore_index), self.shape.vocab, int(off[-1]))
         d_ids = torch.as_tensor(np.ascontiguousarray(ids, np.int32)).to(dev)
         d_lab = torch.as_tensor(np.ascontiguousarray(labels, np.int32)).to(dev)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         self.opts.update = self._update_flag(update)
         d_type = self._set_types(token_types, int(off[-1]))      # noqa: F841
-        _lib.check(self.lib.rs_train_step_mlm(self.handle, _lib.ptr(d_ids), off.ctypes.data, len(off) - 1,
-                                              None if kl is None else kl.ctypes.data, _lib.ptr(d_lab),
-                                              ctypes.byref(self.opts), _lib.ptr(loss), _lib.stream_ptr(dev)))
+        klp = None if kl is None else kl.ctypes.data
+        if rows is None:
+            _lib.check(self.lib.rs_train_step_mlm(self.handle, _lib.ptr(d_ids), off.ctypes.data, len(off) - 1, klp,
+                                                  _lib.ptr(d_lab), ctypes.byref(self.opts), _lib.ptr(loss),
+                                                  _lib.stream_ptr(dev)))
+        else:
+            _lib.check(self.lib.rs_train_step_mlm_labeled(self.handle, _lib.ptr(d_ids), off.ctypes.data, len(off) - 1,
+                                                          klp, rows.ctypes.data, len(rows), _lib.ptr(d_lab),
+                                                          ctypes.byref(self.opts), _lib.ptr(loss),
+                                                          _lib.stream_ptr(dev)))
         return float(loss.item())
 
 
@@ -298,18 +336,96 @@ def rescorebert_epoch(tr: RescoreBertTrainer, tokens, hyp_off, target, am, cer, 
 
 
 def mlm_epoch(tr: MLMTrainer, seqs: Sequence[Sequence[int]], labels: Sequence[Sequence[int]], batch_size: int,
-              update=True, order=None, token_types=None) -> float:
+              update=True, order=None, token_types=None, ignore_index: Optional[int] = None) -> float:
     """One pass of MLM_PLL/main.py:73-114 run_one_epoch (do_scoring False) over do_job rows:
     batches of ``batch_size`` rows (in ``order``, default as given), padded as the reference's
     collate pads them (``pad_rows``).  ``token_types``: a segment-id row per sequence, padded with
-    the ids.  Returns the epoch loss (mean of the batch losses)."""
+    the ids.  ``ignore_index``: labels equal to it carry no loss (``MLMTrainer.step``); the labels are
+    then padded with it, so every batch needs a labelled position.  Returns the epoch loss (mean of
+    the batch losses)."""
     idx = np.arange(len(seqs)) if order is None else np.asarray(order)
     tot, nb = 0.0, 0
     for b0 in range(0, len(idx), batch_size):
         sel = idx[b0:b0 + batch_size]
         tt = None if token_types is None else [token_types[i] for i in sel]
-        ids, off, lab, klen, *typ = pad_rows([seqs[i] for i in sel], [labels[i] for i in sel], tt)
-        tot += tr.step(ids, off, lab, klen, update=update, token_types=typ[0] if typ else None)
+        ids, off, lab, klen, *typ = pad_rows([seqs[i] for i in sel], [labels[i] for i in sel], tt,
+                                             label_pad=0 if ignore_index is None else ignore_index)
+        tot += tr.step(ids, off, lab, klen, update=update, token_types=typ[0] if typ else None,
+                       ignore_index=ignore_index)
+        nb += 1
+    return tot / max(nb, 1)
+
+
+def mask_tokens(seqs: Sequence[Sequence[int]], shape: BertShape, seed, mlm_probability: float = 0.15,
+                continuation: Optional[Sequence[Sequence[int]]] = None
+                ) -> Tuple[List[List[int]], List[List[int]]]:
+    """Dynamic MLM masking of ``[CLS] w.. [SEP]`` rows: the rule of transformers'
+    ``DataCollatorForLanguageModeling.torch_mask_tokens`` on ragged rows, drawn from
+    ``np.random.Generator(PCG64(seed))`` (``seed``: an int or a sequence of ints such as
+    ``(seed, step)``; torch's Bernoulli stream is not reproduced, the rule is).  Position 0 and the
+    last position of each row and any ``[PAD]`` are never selected; every other position is selected
+    with ``mlm_probability``; of the selected, 80 % become ``shape.mask_id``, 10 % a uniform id in
+    ``[0, vocab)`` and 10 % stay.  ``continuation`` (a 0/1 row per sequence, 1 = a ``##`` piece as
+    ``rs_vocab_continuation`` marks it): the selection is drawn per word and covers all its pieces
+    (whole-word masking); the 80/10/10 draw stays per position.  A call that selects nothing selects
+    the eligible position (word) with the smallest draw, so every batch has a label; rows without
+    any eligible position raise ``ValueError``.  Returns (masked rows, label rows): labels are the
+    original id at the selected positions and -100 elsewhere."""
+    if not 0.0 < mlm_probability <= 1.0:
+        raise ValueError("mlm_probability must be in (0, 1]")
+    rng = np.random.Generator(np.random.PCG64(seed))
+    lens = np.asarray([len(s) for s in seqs], np.int64)
+    off = np.concatenate([[0], np.cumsum(lens)])
+    flat = np.concatenate([np.asarray(s, np.int64).reshape(-1) for s in seqs]) if len(seqs) else np.zeros(0, np.int64)
+    elig = flat != shape.pad_id
+    nz = lens > 0
+    elig[off[:-1][nz]] = False
+    elig[off[1:][nz] - 1] = False
+    if continuation is None:
+        starts = np.ones(len(flat), bool)
+    else:
+        cont = np.concatenate([np.asarray(c, np.int64).reshape(-1) for c in continuation])
+        if len(cont) != len(flat):
+            raise ValueError("continuation needs one entry per token")
+        starts = cont == 0
+    # a unit (position, or word) begins at an eligible position that starts a word or follows an
+    # ineligible one; rows are separated by their ineligible first and last positions
+    prev = np.zeros(len(flat), bool)
+    prev[1:] = elig[:-1]
+    ustart = elig & (starts | ~prev)
+    n_unit = int(ustart.sum())
+    if n_unit == 0:
+        raise ValueError("no eligible position (every row is [CLS] [SEP] or padding)")
+    unit = np.maximum(np.cumsum(ustart) - 1, 0)
+    u = rng.random(n_unit)
+    pick = u < mlm_probability
+    if not pick.any():
+        pick[int(np.argmin(u))] = True
+    sel = np.flatnonzero(elig & pick[unit])
+    v = rng.random(len(sel))
+    rid = rng.integers(0, shape.vocab, len(sel))
+    out = flat.copy()
+    out[sel] = np.where(v < 0.8, shape.mask_id, np.where(v < 0.9, rid, flat[sel]))
+    lab = np.full(len(flat), -100, np.int64)
+    lab[sel] = flat[sel]
+    return ([out[off[i]:off[i + 1]].tolist() for i in range(len(seqs))],
+            [lab[off[i]:off[i + 1]].tolist() for i in range(len(seqs))])
+
+
+def mlm_epoch_dynamic(tr: MLMTrainer, sentences: Sequence[Sequence[int]], batch_size: int, seed: Sequence[int],
+                      update=True, order=None, mlm_probability: float = 0.15, continuation=None) -> float:
+    """One pass over ``[CLS] w.. [SEP]`` rows (one per sentence) with dynamic masking: batch b (of
+    ``batch_size`` rows, in ``order``) is masked by ``mask_tokens`` seeded ``(*seed, b)``, so every
+    batch has a labelled position and a pass is a function of ``seed`` alone; labelled steps
+    (``ignore_index`` -100).  Returns the epoch loss (mean of the batch losses)."""
+    idx = np.arange(len(sentences)) if order is None else np.asarray(order)
+    tot, nb = 0.0, 0
+    for b0 in range(0, len(idx), batch_size):
+        sel = idx[b0:b0 + batch_size]
+        rows, labs = mask_tokens([sentences[i] for i in sel], tr.shape, tuple(seed) + (nb,), mlm_probability,
+                                 None if continuation is None else [continuation[i] for i in sel])
+        ids, off, lab, klen = pad_rows(rows, labs, label_pad=-100)
+        tot += tr.step(ids, off, lab, klen, update=update, ignore_index=-100)
         nb += 1
     return tot / max(nb, 1)
 
@@ -330,22 +446,35 @@ def dropout_keep(seed: int, step: int, site: int, p: float, n: int, device=0) ->
 def finetune_mlm_on_texts(weights: Dict[str, np.ndarray], sentences: Sequence[Sequence[int]],
                           shape: BertShape = BERT_BASE, steps: int = 300, batch_size: int = 64,
                           lr: float = 1e-4, seed: int = 0, device=0, dropout: float = 0.0,
-                          log_every: int = 0) -> Tuple[Dict[str, np.ndarray], List[float]]:
+                          log_every: int = 0, masking: str = "do_job", mlm_probability: float = 0.15,
+                          continuation=None) -> Tuple[Dict[str, np.ndarray], List[float]]:
     """MLM fine-tuning on in-domain text, then scoring with the result: the reference's
     pipeline (MLM_PLL/main.py:117-161 mlm_finetune_bert -> :184-186 scoring with that checkpoint ->
     rescore.py:25-45 fusion).  ``sentences`` are word-id lists (no [CLS]/[SEP]); their do_job rows
     (MLM_PLL/preprocess.py:9-30) are visited in a seeded permutation per epoch, ``batch_size``
     padded rows per step (collate, MLM_PLL/main.py:28-54), for ``steps`` AdamW steps.
     Deterministic (native trainer, bitwise reproducible; dropout off by default).  Returns the
-    HF-keyed state dict (loadable by the scorers) and the per-step losses."""
+    HF-keyed state dict (loadable by the scorers) and the per-step losses.
+    ``masking``: "do_job" (default) is the reference's batch, a label at every position, pads
+    included; "do_job_masked" the same rows labelled at their [MASK] only (-100 elsewhere, the head
+    over ``batch_size`` rows); "dynamic" one row per sentence, re-masked every step by
+    ``mask_tokens`` seeded with ``(seed, step)`` (``mlm_probability``; ``continuation``: a 0/1 list
+    per sentence, without [CLS]/[SEP], for whole-word masking)."""
+    if masking not in ("do_job", "do_job_masked", "dynamic"):
+        raise ValueError(f"unknown masking {masking!r} (do_job, do_job_masked, dynamic)")
     seqs, labels = [], []
     for s in sentences:
         h = [shape.cls_id] + [int(x) for x in s] + [shape.sep_id]
+        if masking == "dynamic":
+            seqs.append(h)
+            continue
         for p in range(1, len(h) - 1):
             row = list(h)
             row[p] = shape.mask_id
             seqs.append(row)
-            labels.append(h)
+            labels.append(h if masking == "do_job" else [-100] * p + [h[p]] + [-100] * (len(h) - p - 1))
+    cont = None if continuation is None or masking != "dynamic" else [[0] + [int(x) for x in c] + [0]
+                                                                      for c in continuation]
     tr = MLMTrainer(weights, shape, device=device, lr=lr, hidden_dropout=dropout, attn_dropout=dropout,
                     dropout_seed=seed)
     try:
@@ -356,8 +485,16 @@ def finetune_mlm_on_texts(weights: Dict[str, np.ndarray], sentences: Sequence[Se
             if len(order) < batch_size:
                 order = np.concatenate([order, rng.permutation(len(seqs))])
             sel, order = order[:batch_size], order[batch_size:]
-            ids, off, lab, klen = pad_rows([seqs[i] for i in sel], [labels[i] for i in sel])
-            losses.append(tr.step(ids, off, lab, klen))
+            if masking == "do_job":
+                ids, off, lab, klen = pad_rows([seqs[i] for i in sel], [labels[i] for i in sel])
+                losses.append(tr.step(ids, off, lab, klen))
+            else:
+                rows, labs = [seqs[i] for i in sel], [labels[i] for i in sel] if labels else None
+                if masking == "dynamic":
+                    rows, labs = mask_tokens(rows, shape, (seed, it), mlm_probability,
+                                             None if cont is None else [cont[i] for i in sel])
+                ids, off, lab, klen = pad_rows(rows, labs, label_pad=-100)
+                losses.append(tr.step(ids, off, lab, klen, ignore_index=-100))
             if log_every and (it + 1) % log_every == 0:
                 print(f"finetune step {it + 1}/{steps} loss {losses[-1]:.4f}", flush=True)
         return tr.state_dict(), losses

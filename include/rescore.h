@@ -412,7 +412,32 @@ int rs_train_step_cls(rs_trainer* t, const int32_t* d_tok, const int32_t* h_hyp_
 int rs_train_step_mlm(rs_trainer* t, const int32_t* d_ids, const int32_t* h_seq_off, int32_t n_seq,
                       const int32_t* h_key_len, const int32_t* d_labels, const rs_train_opts* opts,
                       float* d_loss, void* stream);
-/* Segment ids (token_type_ids) of the NEXT rs_train_step_cls / rs_train_step_mlm: d_type int32 [n]
+/* The same step with labels at a caller-given list of token rows only — CrossEntropyLoss's
+ * ignore_index = -100 convention of BertForMaskedLM(input_ids, labels) (modeling_bert.py:972-975),
+ * the -100 positions simply left out of the list.  d_ids, h_seq_off, n_seq, h_key_len, opts, d_loss,
+ * stream: as rs_train_step_mlm.  h_lab_row: host int32 [n_lab], the labelled token rows, indices
+ * into the batch's M = h_seq_off[n_seq] rows, strictly ascending in [0, M); a row past its
+ * sequence's key length (a pad position) is allowed — a query, not a key.  d_lab_id: device int32
+ * [n_lab], the label of each listed row, clamped on the device to [0, vocab).
+ *   loss = (1 / n_lab) sum over the listed rows of (logsumexp(logits) - logits[label]),
+ * the mean over the non-ignored positions.  The transform and the tied decoder run on the n_lab
+ * gathered hidden rows only ([n_lab, vocab] fp32 logits instead of [M, vocab]); the head's gradient
+ * w.r.t. the hidden state is zero at every other row.  Gradients, AdamW, dropout sites and the
+ * dropout-step counter, opts->update in {1, 0, -1}, rs_trainer_set_token_types, the attention form
+ * above 128 tokens and the final synchronise are those of rs_train_step_mlm.  With n_lab == M and
+ * h_lab_row = 0..M-1 the step equals rs_train_step_mlm on the same ids and labels bit for bit (loss,
+ * every gradient, every parameter after the update).
+ * Errors: RS_EARG for n_lab <= 0 (HF's loss is NaN there) and for a row index out of range or not
+ * above its predecessor (the message names the first offending index); RS_ESTATE for a trainer
+ * without the MLM head.  These are raised before any trainer state moves: no parameter, moment or
+ * gradient changes and the dropout-step counter keeps its value, so the next step is the step it
+ * would have been.  The batch errors shared with rs_train_step_mlm (offsets, key lengths, lengths
+ * above max_position_embeddings) change no parameter either but, as there, are raised after a
+ * dropout-active step has taken its key: the counter is then one further. */
+int rs_train_step_mlm_labeled(rs_trainer* t, const int32_t* d_ids, const int32_t* h_seq_off, int32_t n_seq,
+                              const int32_t* h_key_len, const int32_t* h_lab_row, int32_t n_lab,
+                              const int32_t* d_lab_id, const rs_train_opts* opts, float* d_loss, void* stream);
+/* Segment ids (token_type_ids) of the NEXT rs_train_step_cls / rs_train_step_mlm(_labeled): d_type int32 [n]
  * device, one per token row of that step (n must equal its h_off[n_seq], else the step fails with
  * RS_EARG).  One-shot like rs_model_set_token_types: cleared when that step returns, whatever it
  * returns; d_type == NULL clears a pending setting; values are clamped to [0, type_vocab).
