@@ -137,6 +137,36 @@ _DEBUG_SIGS = {
     # (form, qkv, seq_off, klen, n_seq, H, heads, dctx, seed, step, site, p, ctx, dqkv, stream)
     "rs_debug_train_attn": (CI, [CI, P, P, P, CI, CI, CI, P, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32,
                                  ctypes.c_float, P, P, P]),
+    # The trainer's other kernels (csrc/k_train.hip, tests/test_gpu_train_ops.py); dropout = (seed, step, site, p)
+    # (row_tok, row_pos, row_type, M, vocab, type_vocab, max_pos, word, pos, typetab, g, b, eps, H, dropout,
+    #  x0, st, h0, stream)
+    "rs_debug_train_embed_ln": (CI, [P, P, P, CI, CI, CI, CI, P, P, P, P, P, ctypes.c_float, CI, ctypes.c_uint32,
+                                     ctypes.c_uint64, ctypes.c_uint32, ctypes.c_float, P, P, P, P]),
+    # (y, bias, res, M, g, b, eps, H, dropout, st, h, stream)
+    "rs_debug_train_bias_res_ln": (CI, [P, P, P, CI, P, P, ctypes.c_float, CI, ctypes.c_uint32, ctypes.c_uint64,
+                                        ctypes.c_uint32, ctypes.c_float, P, P, P]),
+    # (dy, x, st, g, dx, M, H, stream)
+    "rs_debug_train_ln_bwd": (CI, [P, P, P, P, P, CI, CI, P]),
+    # (op, a, v, c, M, N, stream): 0 bias_gelu(pre, bias, act), 1 gelu_bwd(d, pre), 2 bias(y, bias)
+    "rs_debug_train_pointwise": (CI, [CI, P, P, P, CI, CI, P]),
+    # (op, dy, x, st, M, N, out, out_b, accumulate, rtype, want, stream): 0 / 1 tr_colsum mode, 2 tr_colsum_ln
+    "rs_debug_train_colsum": (CI, [CI, P, P, P, CI, CI, P, P, CI, P, CI, P]),
+    # (dx0, utok, toff, rows, n_uniq, M, vocab, H, dword, stream)
+    "rs_debug_train_word_grad": (CI, [P, P, P, P, CI, CI, CI, CI, P, P]),
+    # (dx0, seq_off, S, M, tmax, H, dpos, stream)
+    "rs_debug_train_pos_grad": (CI, [P, P, CI, CI, CI, CI, P, P]),
+    # (h, seq_off, S, M, H, w, b, out, stream)
+    "rs_debug_train_cls_fwd": (CI, [P, P, CI, CI, CI, P, P, P, P]),
+    # (dsc, h, seq_off, S, M, H, w, dh, dw, db, stream)
+    "rs_debug_train_cls_bwd": (CI, [P, P, P, CI, CI, CI, P, P, P, P, P]),
+    # (sc, tgt, am, cer, utt_off, n_utt, n_hyp, kind, md_w, dsc, uloss, loss, stream)
+    "rs_debug_train_loss": (CI, [P, P, P, P, P, CI, CI, CI, ctypes.c_float, P, P, P, P]),
+    # (logits, labels, M, V, row_loss, loss, stream)
+    "rs_debug_train_ce": (CI, [P, P, CI, CI, P, P, P]),
+    # (op, src, idx, n, M, H, dst, stream): 0 gather_rows, 1 expand_rows
+    "rs_debug_train_move_rows": (CI, [CI, P, P, CI, CI, CI, P, P]),
+    # (p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, stream)
+    "rs_debug_train_adamw": (CI, [P, P, P, P, I64] + [ctypes.c_float] * 5 + [I64, P]),
 }
 
 

@@ -605,7 +605,8 @@ tr_ln_bwd_kernel(const float* dy, const float* __restrict__ x, const float2* __r
 
 // Column reductions, stage 1: partial[rb][c] over rows [64 rb, 64 rb + 64) in row order.
 //   mode 0: sum dy            (bias grads)
-//   mode 1: sum dy * xhat     (LN gamma; xhat from x and (mean, rstd))
+//   mode 1: sum dy * xhat     (LN gamma; xhat from x and (mean, rstd)), accumulated as fmaf(dy, xhat, acc),
+//           written out in both forms: the contraction the compiler made anyway, now not left to it
 // rtype (nullable): row predicate, only rows with rtype[r] == want are summed (the rows are skipped,
 // so the order among the rest is the unpredicated one and a type without rows sums to exactly 0).
 constexpr int kRB = 64;
@@ -629,7 +630,7 @@ __global__ void tr_colsum_partial_kernel(const float* __restrict__ dy, const flo
         for (int r = r0; r < r1; ++r) {
             if (rtype && rtype[r] != want) continue;
             const float2 s = st[r];
-            acc[r & 3] += dy[(size_t)r * N + c] * ((x[(size_t)r * N + c] - s.x) * s.y);
+            acc[r & 3] = fmaf(dy[(size_t)r * N + c], (x[(size_t)r * N + c] - s.x) * s.y, acc[r & 3]);
         }
     }
     part[(size_t)rb * N + c] = (acc[0] + acc[1]) + (acc[2] + acc[3]);
@@ -667,10 +668,10 @@ tr_colsum4_partial_kernel(const float* __restrict__ dy, const float* __restrict_
             if (MODE != 0) {
                 const float2 sr = st[r];
                 const float4 xv = *(const float4*)(x + (size_t)r * N + c);
-                a.x += d.x * ((xv.x - sr.x) * sr.y);
-                a.y += d.y * ((xv.y - sr.x) * sr.y);
-                a.z += d.z * ((xv.z - sr.x) * sr.y);
-                a.w += d.w * ((xv.w - sr.x) * sr.y);
+                a.x = fmaf(d.x, (xv.x - sr.x) * sr.y, a.x);
+                a.y = fmaf(d.y, (xv.y - sr.x) * sr.y, a.y);
+                a.z = fmaf(d.z, (xv.z - sr.x) * sr.y, a.z);
+                a.w = fmaf(d.w, (xv.w - sr.x) * sr.y, a.w);
             }
         }
     }
@@ -904,34 +905,34 @@ __global__ void __launch_bounds__(256) tr_mean_kernel(const float* __restrict__ 
     if (threadIdx.x == 0) out[0] = acc / (float)n;
 }
 
-// torch.optim.AdamW step (decoupled decay, bias-corrected, exp_avg via lerp)
+// torch.optim.AdamW step (decoupled decay, bias-corrected, exp_avg via lerp) of one element.  The
+// fused multiply-adds are written out: left to -ffp-contract the compiler fused them in the float4
+// kernel and not in the scalar one (which it vectorised into separate packed multiplies and adds),
+// so the two forms differed in the last bit of m, v and p (tests/test_gpu_train_ops.py).  These are
+// the contractions the float4 kernel had.
+__device__ __forceinline__ void adamw1(float& pi, float gi, float& mi, float& vi, float decay, float b1w, float b2,
+                                       float b2w, float step_size, float bc2_sqrt, float eps) {
+    mi = fmaf(b1w, gi - mi, mi);
+    vi = fmaf(b2, vi, (b2w * gi) * gi);
+    const float denom = sqrtf(vi) / bc2_sqrt + eps;
+    pi = fmaf(decay, pi, -(step_size * (mi / denom)));
+}
+
 __global__ void tr_adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                 float* __restrict__ v, long long n, float decay, float b1w, float b2, float b2w,
                                 float step_size, float bc2_sqrt, float eps) {
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        float pi = p[i] * decay;
-        const float gi = g[i];
-        const float mi = m[i] + b1w * (gi - m[i]);
-        const float vi = v[i] * b2 + b2w * gi * gi;
+        float pi = p[i], mi = m[i], vi = v[i];
+        adamw1(pi, g[i], mi, vi, decay, b1w, b2, b2w, step_size, bc2_sqrt, eps);
         m[i] = mi;
         v[i] = vi;
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        p[i] = pi - step_size * (mi / denom);
+        p[i] = pi;
     }
 }
 
 // The same update on float4 quads (16-B aligned arrays, n4 = n / 4 quads; the host runs the
 // scalar kernel over the n % 4 tail): every element's arithmetic is the scalar kernel's, bit for
 // bit, at 16-B accesses (the scalar form moved its 28 B per parameter at ≈ 63 % of HBM peak)
-__device__ __forceinline__ float adamw1(float& pi, float gi, float& mi, float& vi, float decay, float b1w, float b2,
-                                        float b2w, float step_size, float bc2_sqrt, float eps) {
-    pi *= decay;
-    mi = mi + b1w * (gi - mi);
-    vi = vi * b2 + b2w * gi * gi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    pi = pi - step_size * (mi / denom);
-    return pi;
-}
 __global__ void tr_adamw4_kernel(float4* __restrict__ p, const float4* __restrict__ g, float4* __restrict__ m,
                                  float4* __restrict__ v, long long n4, float decay, float b1w, float b2, float b2w,
                                  float step_size, float bc2_sqrt, float eps) {
@@ -1080,6 +1081,18 @@ hipError_t tr_attn_bwd_tiled(const float* qkv, const float* P, const float* dctx
 
 int rs_fail(int code, const std::string& msg);
 
+// the test entries' dropout key (p = 0: off)
+static TrDrop debug_drop(unsigned seed, unsigned long long step, unsigned site, float p) {
+    TrDrop d;
+    d.seed = seed;
+    d.step = (uint32_t)step;
+    d.step_hi = (uint32_t)(step >> 32);
+    d.site = site;
+    d.thresh = p <= 0.f ? 0u : (uint32_t)std::min(4294967295.0, (double)p * 4294967296.0);
+    d.scale = (float)(1.0 / (1.0 - (double)p));
+    return d;
+}
+
 // Test entry: attention forward then backward on caller-provided fp32 qkv [M, 3H] and dctx [M, H]
 // (device), seq_off [n_seq + 1] and the nullable klen [n_seq] device int32.  form 0: the
 // whole-head kernels (T <= 128); 1: the tiled kernels.  Dropout (seed, step, site, p), p = 0: off.
@@ -1104,13 +1117,7 @@ extern "C" int rs_debug_train_attn(int form, const float* qkv, const int* seq_of
         pofs[s + 1] = pofs[s] + (long long)heads * T * T;
     }
     if (form == 0 && tmax > 128) return rs_fail(RS_EUNSUP, "form 0 is limited to 128 tokens");
-    TrDrop d;
-    d.seed = seed;
-    d.step = (uint32_t)step;
-    d.step_hi = (uint32_t)(step >> 32);
-    d.site = site;
-    d.thresh = p <= 0.f ? 0u : (uint32_t)std::min(4294967295.0, (double)p * 4294967296.0);
-    d.scale = (float)(1.0 / (1.0 - (double)p));
+    const TrDrop d = debug_drop(seed, step, site, p);
     // scratch (pofs | P | dS): kept and grown between calls, so a timing loop over this entry
     // (tools/train_attn_bench.py) measures the kernels and not hipMalloc / hipFree
     static void* buf = nullptr;
@@ -1287,4 +1294,234 @@ hipError_t tr_dropout_keep(uint8_t* keep, long long n, const TrDrop& d, hipStrea
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(tr_dropout_keep_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, keep, n, d);
     return hipGetLastError();
+}
+
+// ---- Test entries for the non-attention kernels (tests/test_gpu_train_ops.py) -------------------
+// Each runs the launchers above — the functions train_api.hip calls, nothing re-implemented — on
+// caller-provided device buffers (fp32 / int32) and synchronises.  The kernels trust the trainer's
+// host code for their index arrays, so the entries read those back and range-check them first: a
+// bad test input is RS_EARG, not a fault.  Sizes of the float buffers are the caller's promise.
+namespace {
+
+bool dbg_h(int H) { return H == 256 || H == 512 || H == 768 || H == 1024; }
+
+int dbg_ints(const int* d, size_t n, std::vector<int>& h, hipStream_t st) {
+    h.resize(n);
+    if (n == 0) return RS_OK;
+    if (hipMemcpyAsync(h.data(), d, n * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return rs_fail(RS_EHIP, "test entry: reading an index array");
+    return RS_OK;
+}
+
+// offsets: start at 0, ascend (strict: every segment non-empty), end at `end`
+bool dbg_offsets(const std::vector<int>& o, bool strict, long long end) {
+    if (o.empty() || o[0] != 0 || o.back() != end) return false;
+    for (size_t i = 1; i < o.size(); ++i)
+        if (o[i] < o[i - 1] + (strict ? 1 : 0)) return false;
+    return true;
+}
+
+bool dbg_in_range(const std::vector<int>& v, long long lo, long long hi) {       // every value in [lo, hi)
+    for (int x : v)
+        if (x < lo || x >= hi) return false;
+    return true;
+}
+
+int dbg_done(hipError_t e, hipStream_t st, const char* what) {
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return rs_fail(RS_EHIP, std::string(what) + ": " + hipGetErrorString(e));
+    return RS_OK;
+}
+
+bool dbg_p(float p) { return p >= 0.f && p < 1.f; }
+
+}  // namespace
+
+// x0 [M, H], st [M, 2] (mean, rstd), h0 [M, H] of tr_embed_ln; word [vocab, H], pos [max_pos, H],
+// typetab [type_vocab, H]; row_type nullable.  Dropout (seed, step, site, p), p = 0: off.
+extern "C" int rs_debug_train_embed_ln(const int* row_tok, const int* row_pos, const int* row_type, int M, int vocab,
+                                       int type_vocab, int max_pos, const float* word, const float* pos,
+                                       const float* typetab, const float* g, const float* b, float eps, int H,
+                                       unsigned seed, unsigned long long step, unsigned site, float p, float* x0,
+                                       float* st, float* h0, void* stream) {
+    if (!row_tok || !row_pos || !word || !pos || !typetab || !g || !b || !x0 || !st || !h0)
+        return rs_fail(RS_EARG, "null argument");
+    if (M <= 0 || vocab <= 0 || type_vocab <= 0 || max_pos <= 0) return rs_fail(RS_EARG, "empty shape");
+    if (!dbg_h(H)) return rs_fail(RS_EUNSUP, "hidden must be 256, 512, 768 or 1024");
+    if (!dbg_p(p)) return rs_fail(RS_EARG, "p must be in [0, 1)");
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int> hp;
+    if (int r = dbg_ints(row_pos, (size_t)M, hp, s)) return r;
+    if (!dbg_in_range(hp, 0, max_pos)) return rs_fail(RS_EARG, "row_pos outside [0, max_pos)");
+    return dbg_done(tr_embed_ln(row_tok, row_pos, row_type, M, vocab, type_vocab, word, pos, typetab, g, b, eps, H,
+                                x0, (float2*)st, h0, s, debug_drop(seed, step, site, p)),
+                    s, "rs_debug_train_embed_ln");
+}
+
+// y [M, H] in place, st [M, 2], h [M, H] of tr_bias_res_ln; bias == null: plain LayerNorm of y
+// (res unused, no dropout)
+extern "C" int rs_debug_train_bias_res_ln(float* y, const float* bias, const float* res, int M, const float* g,
+                                          const float* b, float eps, int H, unsigned seed, unsigned long long step,
+                                          unsigned site, float p, float* st, float* h, void* stream) {
+    if (!y || !g || !b || !st || !h || (bias && !res)) return rs_fail(RS_EARG, "null argument");
+    if (M <= 0) return rs_fail(RS_EARG, "empty shape");
+    if (!dbg_h(H)) return rs_fail(RS_EUNSUP, "hidden must be 256, 512, 768 or 1024");
+    if (!dbg_p(p)) return rs_fail(RS_EARG, "p must be in [0, 1)");
+    hipStream_t s = (hipStream_t)stream;
+    return dbg_done(tr_bias_res_ln(y, bias, res, M, g, b, eps, H, (float2*)st, h, s, debug_drop(seed, step, site, p)),
+                    s, "rs_debug_train_bias_res_ln");
+}
+
+// dx [M, H] of tr_ln_bwd (dx may be dy)
+extern "C" int rs_debug_train_ln_bwd(const float* dy, const float* x, const float* st, const float* g, float* dx,
+                                     int M, int H, void* stream) {
+    if (!dy || !x || !st || !g || !dx) return rs_fail(RS_EARG, "null argument");
+    if (M <= 0) return rs_fail(RS_EARG, "empty shape");
+    if (!dbg_h(H)) return rs_fail(RS_EUNSUP, "hidden must be 256, 512, 768 or 1024");
+    hipStream_t s = (hipStream_t)stream;
+    return dbg_done(tr_ln_bwd(dy, x, (const float2*)st, g, dx, M, H, s), s, "rs_debug_train_ln_bwd");
+}
+
+// op 0: tr_bias_gelu(pre = a, bias = v, act = c); 1: tr_gelu_bwd(d = a, pre = v); 2: tr_bias(y = a,
+// bias = v).  a, c [M, N]; v [N] (op 1: [M, N]).
+extern "C" int rs_debug_train_pointwise(int op, float* a, const float* v, float* c, int M, int N, void* stream) {
+    if (op < 0 || op > 2) return rs_fail(RS_EARG, "op must be 0, 1 or 2");
+    if (!a || !v || (op == 0 && !c)) return rs_fail(RS_EARG, "null argument");
+    if (M <= 0 || N <= 0) return rs_fail(RS_EARG, "empty shape");
+    if (N % 4) return rs_fail(RS_EUNSUP, "N must be a multiple of 4");
+    hipStream_t s = (hipStream_t)stream;
+    const hipError_t e = op == 0 ? tr_bias_gelu(a, v, c, M, N, s)
+                         : op == 1 ? tr_gelu_bwd(a, v, (long long)M * N, s)
+                                   : tr_bias(a, v, M, N, s);
+    return dbg_done(e, s, "rs_debug_train_pointwise");
+}
+
+// op 0 / 1: tr_colsum of that mode into out [N] (accumulate: added to it), over the rows with
+// rtype[r] == want when rtype is given; op 2: tr_colsum_ln into out (gamma) and out_b (beta).
+// dy, x [M, N], st [M, 2] (x, st: ops 1 and 2).  The scratch is sized by tr_colsum_scratch.
+extern "C" int rs_debug_train_colsum(int op, const float* dy, const float* x, const float* st, int M, int N,
+                                     float* out, float* out_b, int accumulate, const int* rtype, int want,
+                                     void* stream) {
+    if (op < 0 || op > 2) return rs_fail(RS_EARG, "op must be 0, 1 or 2");
+    if (!dy || !out || (op != 0 && (!x || !st)) || (op == 2 && !out_b)) return rs_fail(RS_EARG, "null argument");
+    if (op == 2 && (rtype || accumulate)) return rs_fail(RS_EARG, "tr_colsum_ln takes no row predicate / accumulate");
+    if (M <= 0 || N <= 0) return rs_fail(RS_EARG, "empty shape");
+    hipStream_t s = (hipStream_t)stream;
+    float* part = nullptr;
+    if (hipMalloc((void**)&part, tr_colsum_scratch(M, N)) != hipSuccess) {
+        (void)hipGetLastError();
+        return rs_fail(RS_ENOMEM, "rs_debug_train_colsum: scratch");
+    }
+    const hipError_t e = op == 2 ? tr_colsum_ln(dy, x, (const float2*)st, M, N, part, out, out_b, s)
+                                 : tr_colsum(dy, x, (const float2*)st, M, N, op, part, out, accumulate, s, rtype, want);
+    const int r = dbg_done(e, s, "rs_debug_train_colsum");
+    (void)hipFree(part);
+    return r;
+}
+
+// dword [vocab, H] += tr_word_grad of dx0 [M, H]: utok [n_uniq] distinct token ids, toff
+// [n_uniq + 1] offsets into rows (the row indices of each token, in row order)
+extern "C" int rs_debug_train_word_grad(const float* dx0, const int* utok, const int* toff, const int* rows,
+                                        int n_uniq, int M, int vocab, int H, float* dword, void* stream) {
+    if (!dx0 || !utok || !toff || !rows || !dword) return rs_fail(RS_EARG, "null argument");
+    if (n_uniq <= 0 || M <= 0 || vocab <= 0 || H <= 0) return rs_fail(RS_EARG, "empty shape");
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int> hu, ho, hr;
+    if (int r = dbg_ints(utok, (size_t)n_uniq, hu, s)) return r;
+    if (int r = dbg_ints(toff, (size_t)n_uniq + 1, ho, s)) return r;
+    if (!dbg_in_range(hu, 0, vocab) || ho[0] != 0 || !dbg_offsets(ho, false, ho.back()))
+        return rs_fail(RS_EARG, "token ids / offsets out of range");
+    if (int r = dbg_ints(rows, (size_t)ho.back(), hr, s)) return r;
+    if (!dbg_in_range(hr, 0, M)) return rs_fail(RS_EARG, "row index outside [0, M)");
+    return dbg_done(tr_word_grad(dx0, utok, toff, rows, n_uniq, H, dword, s), s, "rs_debug_train_word_grad");
+}
+
+// dpos [tmax, H] += tr_pos_grad of dx0 [seq_off[S], H]
+extern "C" int rs_debug_train_pos_grad(const float* dx0, const int* seq_off, int S, int M, int tmax, int H,
+                                       float* dpos, void* stream) {
+    if (!dx0 || !seq_off || !dpos) return rs_fail(RS_EARG, "null argument");
+    if (S <= 0 || M <= 0 || tmax <= 0 || H <= 0) return rs_fail(RS_EARG, "empty shape");
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int> ho;
+    if (int r = dbg_ints(seq_off, (size_t)S + 1, ho, s)) return r;
+    if (!dbg_offsets(ho, true, M)) return rs_fail(RS_EARG, "offsets must start at 0, ascend and end at M");
+    return dbg_done(tr_pos_grad(dx0, seq_off, S, tmax, H, dpos, s), s, "rs_debug_train_pos_grad");
+}
+
+// out [S] = tr_cls_fwd of h [M, H] (the CLS row of sequence s is seq_off[s])
+extern "C" int rs_debug_train_cls_fwd(const float* h, const int* seq_off, int S, int M, int H, const float* w,
+                                      const float* b, float* out, void* stream) {
+    if (!h || !seq_off || !w || !b || !out) return rs_fail(RS_EARG, "null argument");
+    if (S <= 0 || M <= 0 || H <= 0) return rs_fail(RS_EARG, "empty shape");
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int> ho;
+    if (int r = dbg_ints(seq_off, (size_t)S + 1, ho, s)) return r;
+    if (!dbg_offsets(ho, true, M)) return rs_fail(RS_EARG, "offsets must start at 0, ascend and end at M");
+    return dbg_done(tr_cls_fwd(h, seq_off, S, H, w, b, out, s), s, "rs_debug_train_cls_fwd");
+}
+
+// tr_cls_bwd: dh [M, H] (zeroed by the caller) at the CLS rows, dw [H] and db [1] added to
+extern "C" int rs_debug_train_cls_bwd(const float* dsc, const float* h, const int* seq_off, int S, int M, int H,
+                                      const float* w, float* dh, float* dw, float* db, void* stream) {
+    if (!dsc || !h || !seq_off || !w || !dh || !dw || !db) return rs_fail(RS_EARG, "null argument");
+    if (S <= 0 || M <= 0 || H <= 0) return rs_fail(RS_EARG, "empty shape");
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int> ho;
+    if (int r = dbg_ints(seq_off, (size_t)S + 1, ho, s)) return r;
+    if (!dbg_offsets(ho, true, M)) return rs_fail(RS_EARG, "offsets must start at 0, ascend and end at M");
+    return dbg_done(tr_cls_bwd(dsc, h, seq_off, S, H, w, dh, dw, db, s), s, "rs_debug_train_cls_bwd");
+}
+
+// tr_loss: sc, tgt, am, cer, dsc [n_hyp]; utt_off [n_utt + 1] (empty groups allowed); uloss [n_utt];
+// loss [1].  kind: RS_LOSS_MD / _MWER / _MWED.
+extern "C" int rs_debug_train_loss(const float* sc, const float* tgt, const float* am, const float* cer,
+                                   const int* utt_off, int n_utt, int n_hyp, int kind, float md_w, float* dsc,
+                                   float* uloss, float* loss, void* stream) {
+    if (!sc || !tgt || !am || !cer || !utt_off || !dsc || !uloss || !loss) return rs_fail(RS_EARG, "null argument");
+    if (n_utt <= 0 || n_hyp <= 0) return rs_fail(RS_EARG, "empty shape");
+    if (kind != RS_LOSS_MD && kind != RS_LOSS_MWER && kind != RS_LOSS_MWED) return rs_fail(RS_EARG, "unknown loss");
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int> ho;
+    if (int r = dbg_ints(utt_off, (size_t)n_utt + 1, ho, s)) return r;
+    if (!dbg_offsets(ho, false, n_hyp)) return rs_fail(RS_EARG, "offsets must start at 0, not descend and end at n_hyp");
+    return dbg_done(tr_loss(sc, tgt, am, cer, utt_off, n_utt, n_hyp, kind, md_w, dsc, uloss, loss, s), s,
+                    "rs_debug_train_loss");
+}
+
+// tr_ce: logits [M, V] replaced by d loss / d logits, row_loss [M], loss [1] (their mean)
+extern "C" int rs_debug_train_ce(float* logits, const int* labels, int M, int V, float* row_loss, float* loss,
+                                 void* stream) {
+    if (!logits || !labels || !row_loss || !loss) return rs_fail(RS_EARG, "null argument");
+    if (M <= 0 || V <= 0) return rs_fail(RS_EARG, "empty shape");
+    hipStream_t s = (hipStream_t)stream;
+    return dbg_done(tr_ce(logits, labels, M, V, row_loss, loss, s), s, "rs_debug_train_ce");
+}
+
+// op 0: tr_gather_rows, dst [n, H] = src [M, H] at idx [n] (rows in [0, M)); 1: tr_expand_rows,
+// dst [M, H] = src [n, H] at idx [M] (in [0, n), or negative: a zero row)
+extern "C" int rs_debug_train_move_rows(int op, const float* src, const int* idx, int n, int M, int H, float* dst,
+                                        void* stream) {
+    if (op < 0 || op > 1) return rs_fail(RS_EARG, "op must be 0 or 1");
+    if (!src || !idx || !dst) return rs_fail(RS_EARG, "null argument");
+    if (n <= 0 || M <= 0 || H <= 0) return rs_fail(RS_EARG, "empty shape");
+    if (H % 4) return rs_fail(RS_EUNSUP, "H must be a multiple of 4");
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int> hi;
+    if (int r = dbg_ints(idx, (size_t)(op == 0 ? n : M), hi, s)) return r;
+    if (!dbg_in_range(hi, op == 0 ? 0 : -2147483648LL, op == 0 ? M : n)) return rs_fail(RS_EARG, "row index out of range");
+    return dbg_done(op == 0 ? tr_gather_rows(src, idx, n, H, dst, s) : tr_expand_rows(src, idx, M, H, dst, s), s,
+                    "rs_debug_train_move_rows");
+}
+
+// One torch.optim.AdamW step, number `step` (1-based), on p, g, m, v [n]: the optimizer's own
+// hyper-parameters, turned into the kernel's scalars by tr_adamw_scalars as the trainer does
+extern "C" int rs_debug_train_adamw(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1,
+                                    float beta2, float eps, float weight_decay, long long step, void* stream) {
+    if (!p || !g || !m || !v) return rs_fail(RS_EARG, "null argument");
+    if (n <= 0 || step < 1) return rs_fail(RS_EARG, "n and step must be positive");
+    hipStream_t s = (hipStream_t)stream;
+    const TrAdamW a = tr_adamw_scalars(lr, beta1, beta2, eps, weight_decay, step);
+    return dbg_done(tr_adamw(p, g, m, v, n, a.decay, a.b1w, a.b2, a.b2w, a.step_size, a.bc2_sqrt, a.eps, s), s,
+                    "rs_debug_train_adamw");
 }

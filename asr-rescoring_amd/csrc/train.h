@@ -12,6 +12,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cmath>
 #include "../../include/rescore.h"
 
 // Dropout of BERT's train mode (modeling_bert.py: BertEmbeddings.dropout after the LayerNorm,
@@ -112,6 +113,24 @@ hipError_t tr_gather_rows(const float* src, const int* rows, int n, int H, float
 hipError_t tr_expand_rows(const float* src, const int* inv, int M, int H, float* dst, hipStream_t s);
 hipError_t tr_adamw(float* p, const float* g, float* m, float* v, long long n, float decay, float b1w, float b2,
                     float b2w, float step_size, float bc2_sqrt, float eps, hipStream_t s);
+// tr_adamw's scalars for optimizer step `step` (1-based) of torch.optim.AdamW: python-float
+// (double) scalars as torch computes them, cast to the fp32 tensor dtype
+struct TrAdamW {
+    float decay, b1w, b2, b2w, step_size, bc2_sqrt, eps;
+};
+inline TrAdamW tr_adamw_scalars(float lr, float beta1, float beta2, float eps, float weight_decay, long long step) {
+    const double bc1 = 1.0 - std::pow((double)beta1, (double)step);
+    const double bc2 = 1.0 - std::pow((double)beta2, (double)step);
+    TrAdamW a;
+    a.decay = (float)(1.0 - (double)lr * (double)weight_decay);
+    a.b1w = (float)(1.0 - (double)beta1);
+    a.b2 = beta2;
+    a.b2w = (float)(1.0 - (double)beta2);
+    a.step_size = (float)((double)lr / bc1);
+    a.bc2_sqrt = (float)std::sqrt(bc2);
+    a.eps = eps;
+    return a;
+}
 // fp32 GEMM on the f32-input MFMA (k_sgemm.hip): C[M][N] = A·B (+ C when accum), A read as
 // [M][lda] with k contiguous (a_kc) or [K][lda] with rows contiguous, B as [N][ldb] (b_kc)
 // or [K][ldb].  Few output tiles are split over K through ws (tr_sgemm_ws_floats floats),

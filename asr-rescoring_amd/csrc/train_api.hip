@@ -637,13 +637,9 @@ int encoder_backward(StepCtx& c) {
 int adamw(rs_trainer* t, const rs_train_opts* o, hipStream_t st) {
     if (o->update != 1) return RS_OK;
     t->step += 1;
-    const double bc1 = 1.0 - std::pow((double)o->beta1, (double)t->step);
-    const double bc2 = 1.0 - std::pow((double)o->beta2, (double)t->step);
-    // python-float (double) scalars as torch computes them, cast to the fp32 tensor dtype
-    const float decay = (float)(1.0 - (double)o->lr * (double)o->weight_decay);
+    const TrAdamW a = tr_adamw_scalars(o->lr, o->beta1, o->beta2, o->eps, o->weight_decay, t->step);
     TRY_HIP(tr_adamw(t->P.as<float>(), t->G.as<float>(), t->M1.as<float>(), t->V1.as<float>(), (long long)t->n_params,
-                     decay, (float)(1.0 - (double)o->beta1), o->beta2, (float)(1.0 - (double)o->beta2),
-                     (float)((double)o->lr / bc1), (float)std::sqrt(bc2), o->eps, st));
+                     a.decay, a.b1w, a.b2, a.b2w, a.step_size, a.bc2_sqrt, a.eps, st));
     return RS_OK;
 }
 
