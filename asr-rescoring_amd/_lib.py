@@ -167,6 +167,11 @@ _DEBUG_SIGS = {
     "rs_debug_train_move_rows": (CI, [CI, P, P, CI, CI, CI, P, P]),
     # (p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, stream)
     "rs_debug_train_adamw": (CI, [P, P, P, P, I64] + [ctypes.c_float] * 5 + [I64, P]),
+    # The BERTScore kernels without an encoder (tests/test_gpu_bertscore_ops.py)
+    # (d_emb, H, two, h_hyp_off, h_utt_off, n_utt, d_rmat, d_rmat0, stream)
+    "rs_debug_bertscore_recall": (CI, [P, CI, CI, P, P, CI, P, P, P]),
+    # (x32, stats, g, b, himg, len, row, tok_off, s0, s1, row0, H, two, d_out, stream)
+    "rs_debug_embed_out": (CI, [P, P, P, P, P, P, P, P, CI, CI, CI, CI, CI, P, P]),
 }
 
 

@@ -723,3 +723,22 @@ extern "C" int rs_debug_ln(int kind, int rows, float* x32, float2* stats, float2
     }
     return e == hipSuccess ? 0 : -2;
 }
+
+// Test entry (not part of the scoring path): embed_out_kernel through the production launcher over
+// sequences [s0, s1) of the device metadata arrays len / row / tok_off (each [>= s1]).  The row of
+// position t of sequence s is row[s] - row0 + t in the source: (x32 [rows, H], stats [rows], g, b
+// [H]) or, himg != null, the interleaved two-part image [rows, 2H].  out: fp16 [tokens, H], or
+// (two != 0) the planar two-part image [tokens, 2H], written at token tok_off[s] + t.
+extern "C" int rs_debug_embed_out(const float* x32, const void* stats, const float* g, const float* b, const void* himg,
+                                  const int* len, const int* row, const int* tok_off, int s0, int s1, int row0, int H,
+                                  int two, void* d_out, void* stream) {
+    if (!len || !row || !tok_off || !d_out || s0 < 0 || s1 <= s0) return -1;
+    if (!himg && (!x32 || !stats || !g || !b)) return -1;
+    SeqMeta sm{};
+    sm.len = len;
+    sm.row = row;
+    sm.tok_off = tok_off;
+    const hipError_t e = launch_embed_out(x32, (const float2*)stats, g, b, sm, s0, s1, row0, H, (f16*)d_out,
+                                          (hipStream_t)stream, (const f16*)himg, two != 0);
+    return e == hipSuccess ? 0 : -2;
+}

@@ -15,6 +15,7 @@
 
 #include "common.h"
 #include "seq_plan.h"
+#include "bertscore_plan.h"
 #include "host_util.h"
 
 namespace {
@@ -1348,63 +1349,74 @@ int rs_token_embed(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off, 
     return token_embed(m, (hipStream_t)stream, call, h_hyp_off, n_hyp, d_emb);
 }
 
+// The recall launch over an embedding buffer: the plan (bertscore_plan.h: runs of whole ref
+// hypotheses fitting one COLS-column tile, a longer one alone), one upload through `stage` into
+// `plan`, the kernel.  m: the model whose profile records the launch, or null.
+static int recall_launch(rs_model* m, Staging& stage, DevBuf& plan, const f16* emb, int H, bool two,
+                         const int32_t* h_hyp_off, const int32_t* h_utt_off, int n_utt, float* d_rmat, float* d_rmat0,
+                         hipStream_t st) {
+    const int n_hyp = h_utt_off[n_utt];
+    BertscorePlan bp;
+    plan_bertscore_items(h_hyp_off, h_utt_off, n_utt, bertscore_cols(two), &bp);
+    const BertscoreUpload w = bertscore_upload_layout(bp, n_hyp, n_utt);
+    TRY_HIP(stage.begin(w.n_int));
+    bertscore_upload_pack(bp, w, h_hyp_off, h_utt_off, n_hyp, n_utt, stage.p);
+    TRY_HIP(stage.upload(plan, w.n_int, st));
+    const int* d = plan.as<int>();
+    auto go = [&] {
+        return launch_bertscore_recall(emb, H, d + w.hyp_off, d + w.utt_off, (const long long*)(d + w.moff),
+                                       (const int4*)(d + w.items), bp.n_items(), d_rmat, d_rmat0, st, two);
+    };
+    if (m) LAUNCH_OTHER(go());
+    else TRY_HIP(go());
+    return RS_OK;
+}
+
 int rs_bertscore_recall(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_off,
                         const int32_t* h_utt_off, int32_t n_utt, float* d_rmat, float* d_rmat0, void* stream) {
     PendingTypes ty(m);
     if (!m || !h_hyp_off || !h_utt_off || n_utt < 0 || (n_utt > 0 && (!d_tok || !d_rmat)))
         return fail(RS_EARG, "null argument");
     if (n_utt == 0) return RS_OK;
-    if (h_utt_off[0] != 0) return fail(RS_EARG, "utt_off[0] must be 0");
+    const std::string bad = bertscore_layout_error(h_hyp_off, h_utt_off, n_utt);
+    if (!bad.empty()) return fail(RS_EARG, bad);
     const int n_hyp = h_utt_off[n_utt];
-    for (int u = 0; u < n_utt; ++u)
-        if (h_utt_off[u + 1] < h_utt_off[u]) return fail(RS_EARG, "utt_off not ascending");
-    if (h_hyp_off[0] != 0) return fail(RS_EARG, "hyp_off[0] must be 0");
-    for (int h = 0; h < n_hyp; ++h)
-        if (h_hyp_off[h + 1] - h_hyp_off[h] < 2)
-            return fail(RS_EARG, "hypothesis " + std::to_string(h) + " has fewer than 2 tokens ([CLS] [SEP])");
     hipStream_t st = (hipStream_t)stream;
     CALL_ORDER(m, st);
     const int H = m->cfg.hidden;
     const size_t n_tok = (size_t)h_hyp_off[n_hyp];
     const bool two = m->kx == 3;                 // fp16x3: two-part embeddings, split-operand cosines
-    const int COLS = bertscore_cols(two);
     TRY_HIP(m->emb.ensure(std::max<size_t>(n_tok, 1) * H * 2 * (two ? 2 : 1)));
     if (n_hyp > 0) {
         Call call{MODE_EMB, d_tok};
         if (int r = ty.take(h_hyp_off[n_hyp], &call)) return r;
         if (int r = token_embed(m, st, call, h_hyp_off, n_hyp, m->emb.p)) return r;
     }
-    // plan: runs of whole ref hypotheses fitting one COLS-column tile (a longer one alone)
-    std::vector<int> items;
-    std::vector<long long> moff(n_utt + 1, 0);
-    for (int u = 0; u < n_utt; ++u) {
-        const int h0 = h_utt_off[u], n = h_utt_off[u + 1] - h0;
-        moff[u + 1] = moff[u] + (long long)n * n;
-        for (int j = 0; j < n;) {
-            int j1 = j + 1, cols = h_hyp_off[h0 + j + 1] - h_hyp_off[h0 + j];
-            while (cols <= COLS && j1 < n && cols + h_hyp_off[h0 + j1 + 1] - h_hyp_off[h0 + j1] <= COLS) {
-                cols += h_hyp_off[h0 + j1 + 1] - h_hyp_off[h0 + j1];
-                ++j1;
-            }
-            items.insert(items.end(), {u, j, j1, 0});
-            j = j1;
-        }
-    }
-    const int n_items = (int)(items.size() / 4);
-    // one upload: items | mat_off (int64) | hyp_off | utt_off
-    const size_t w_items = items.size(), w_moff = 2 * (size_t)(n_utt + 1);
-    const size_t n_int = w_items + w_moff + (size_t)(n_hyp + 1) + (size_t)(n_utt + 1);
-    TRY_HIP(m->stage_plan.begin(n_int));
-    int* p = m->stage_plan.p;
-    std::memcpy(p, items.data(), w_items * 4);
-    std::memcpy(p + w_items, moff.data(), w_moff * 4);
-    std::memcpy(p + w_items + w_moff, h_hyp_off, (size_t)(n_hyp + 1) * 4);
-    std::memcpy(p + w_items + w_moff + n_hyp + 1, h_utt_off, (size_t)(n_utt + 1) * 4);
-    TRY_HIP(m->stage_plan.upload(m->plan, n_int, st));
-    int* d = m->plan.as<int>();
-    LAUNCH_OTHER(launch_bertscore_recall(m->emb.as<f16>(), H, d + w_items + w_moff, d + w_items + w_moff + n_hyp + 1,
-                                         (const long long*)(d + w_items), (const int4*)d, n_items, d_rmat, d_rmat0, st,
-                                         two));
+    return recall_launch(m, m->stage_plan, m->plan, m->emb.as<f16>(), H, two, h_hyp_off, h_utt_off, n_utt, d_rmat,
+                         d_rmat0, st);
+}
+
+// Test entry (not part of the scoring path): the recall kernel on the caller's embedding buffer
+// d_emb [hyp_off[n_hyp], H] fp16, or (two != 0) the planar two-part image [.., 2H] — the layout
+// checks, the plan, the upload and the launch of rs_bertscore_recall without its encoder.
+// Synchronises the stream before it returns (the plan buffers are the call's own).
+int rs_debug_bertscore_recall(const void* d_emb, int32_t H, int32_t two, const int32_t* h_hyp_off,
+                              const int32_t* h_utt_off, int32_t n_utt, float* d_rmat, float* d_rmat0, void* stream) {
+    if (!h_hyp_off || !h_utt_off || n_utt < 0 || (n_utt > 0 && (!d_emb || !d_rmat)))
+        return fail(RS_EARG, "null argument");
+    if (H <= 0 || H % 256 || H > 1024) return fail(RS_EUNSUP, "hidden must be 256/512/768/1024");
+    if (n_utt == 0) return RS_OK;
+    const std::string bad = bertscore_layout_error(h_hyp_off, h_utt_off, n_utt);
+    if (!bad.empty()) return fail(RS_EARG, bad);
+    hipStream_t st = (hipStream_t)stream;
+    Staging stage;
+    DevBuf plan;
+    const int r = recall_launch(nullptr, stage, plan, (const f16*)d_emb, H, two != 0, h_hyp_off, h_utt_off, n_utt,
+                                d_rmat, d_rmat0, st);
+    const hipError_t e = hipStreamSynchronize(st);
+    plan.release();
+    if (r) return r;
+    TRY_HIP(e);
     return RS_OK;
 }
 
