@@ -44,8 +44,16 @@ class RsTrainOpts(ctypes.Structure):
                 ("dropout_seed", ctypes.c_uint32)]
 
 
+class RsApplyOpts(ctypes.Structure):
+    _fields_ = [("source", ctypes.c_int32), ("grad_scale", ctypes.c_float), ("max_grad_norm", ctypes.c_float)]
+
+
 class RescoreError(RuntimeError):
-    pass
+    """A failed library call; ``code`` is the RS_E* value (``RS_ESTATE`` = -3, ...)."""
+
+    def __init__(self, msg, code=None):
+        super().__init__(msg)
+        self.code = code
 
 
 _lib = None
@@ -86,6 +94,14 @@ _SIGS = {
     "rs_train_step_mlm_labeled": (ctypes.c_int, [P, P, P, I32, P, P, I32, P, ctypes.POINTER(RsTrainOpts), P, P]),
     "rs_trainer_get_tensor": (ctypes.c_int, [P, ctypes.c_char_p, P, I64]),
     "rs_trainer_get_grad": (ctypes.c_int, [P, ctypes.c_char_p, P, I64]),
+    "rs_trainer_set_trainable": (ctypes.c_int, [P, ctypes.c_char_p, I32]),
+    "rs_trainer_is_trainable": (ctypes.c_int, [P, ctypes.c_char_p]),
+    "rs_trainer_accumulate": (ctypes.c_int, [P, ctypes.c_float, P]),
+    "rs_trainer_zero_accum": (ctypes.c_int, [P]),
+    "rs_trainer_get_accum": (ctypes.c_int, [P, ctypes.c_char_p, P, I64]),
+    "rs_trainer_apply": (ctypes.c_int, [P, ctypes.POINTER(RsTrainOpts), ctypes.POINTER(RsApplyOpts),
+                                        ctypes.POINTER(ctypes.c_double), ctypes.POINTER(I32), P]),
+    "rs_trainer_grad_norm": (ctypes.c_int, [P, I32, ctypes.POINTER(ctypes.c_double), P]),
     "rs_trainer_reset_optimizer": (ctypes.c_int, [P]),
     "rs_trainer_set_token_types": (ctypes.c_int, [P, P, I64]),
     "rs_trainer_dropout_step": (I64, [P]),
@@ -167,6 +183,12 @@ _DEBUG_SIGS = {
     "rs_debug_train_move_rows": (CI, [CI, P, P, CI, CI, CI, P, P]),
     # (p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, stream)
     "rs_debug_train_adamw": (CI, [P, P, P, P, I64] + [ctypes.c_float] * 5 + [I64, P]),
+    # (p, g, m, v, n, gmul, lr, beta1, beta2, eps, weight_decay, step, stream)
+    "rs_debug_train_adamw_scaled": (CI, [P, P, P, P, I64] + [ctypes.c_float] * 6 + [I64, P]),
+    # (acc, g, h_off, h_n, n_ranges, n_total, w, stream): host int64 range lists
+    "rs_debug_train_accum": (CI, [P, P, P, P, CI, I64, ctypes.c_float, P]),
+    # (g, h_off, h_n, n_ranges, n_total, h_out, stream): h_out host float64 [1]
+    "rs_debug_train_sumsq": (CI, [P, P, P, CI, I64, P, P]),
     # The BERTScore kernels without an encoder (tests/test_gpu_bertscore_ops.py)
     # (d_emb, H, two, h_hyp_off, h_utt_off, n_utt, d_rmat, d_rmat0, stream)
     "rs_debug_bertscore_recall": (CI, [P, CI, CI, P, P, CI, P, P, P]),
@@ -211,7 +233,7 @@ def load(path: str = LIB_PATH):
 
 def check(rc: int) -> None:
     if rc != 0:
-        raise RescoreError(f"librescore error {rc}: {load().rs_last_error().decode()}")
+        raise RescoreError(f"librescore error {rc}: {load().rs_last_error().decode()}", rc)
 
 
 def bert_cfg(shape, heads: int, precision: str = "fp16") -> RsBertCfg:

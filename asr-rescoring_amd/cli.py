@@ -294,6 +294,40 @@ def _dropout_args(cfg) -> Dict[str, float]:
             "dropout_seed": int(get(cfg, "dropout_seed", get(cfg, "seed", 0)))}
 
 
+def _optim_plan(cfg, tr, n_batches: int, epochs: int):
+    """The optimizer options both trainers share: ``accum_steps`` (default 1: batches per optimizer
+    step, the gradients accumulated), ``max_grad_norm`` (default none: ``clip_grad_norm_`` before each
+    step), ``lr_schedule`` (``constant``, default, or ``linear`` with ``warmup_steps``: the
+    ``get_linear_schedule_with_warmup`` multiplier on ``lr`` over the whole run, epochs x optimizer
+    steps per epoch, so a resumed run starts at its epoch's first global step) and ``freeze`` (a list
+    of key prefixes, ``_Trainer.freeze``; the reference's ``util/freezer.py`` names).  Freezes now;
+    returns ``epoch -> keyword arguments`` of the epoch helper (none without the keys: the run and its
+    ``loss.json`` are then unchanged)."""
+    from .train import lr_at
+    accum = int(get(cfg, "accum_steps", 1))
+    clip = get(cfg, "max_grad_norm")
+    schedule = str(get(cfg, "lr_schedule", "constant"))
+    warmup = int(get(cfg, "warmup_steps", 0))
+    if accum < 1 or schedule not in ("constant", "linear"):
+        raise ValueError("accum_steps must be at least 1 and lr_schedule constant or linear")
+    frz = get(cfg, "freeze") or []
+    tr.freeze(*([frz] if isinstance(frz, str) else list(frz)))
+    per_epoch = -(-n_batches // accum)
+    base_lr = float(get(cfg, "lr", 1e-5))
+
+    def kwargs(ep: int):
+        kw = {}
+        if accum != 1:
+            kw["accum_steps"] = accum
+        if clip is not None:
+            kw["max_grad_norm"] = float(clip)
+        if schedule != "constant":
+            first = (ep - 1) * per_epoch
+            kw["lr_of_step"] = lambda k: lr_at(first + k, epochs * per_epoch, warmup, base_lr, schedule)
+        return kw
+    return kwargs
+
+
 def mlm_finetune(cfg) -> Dict[str, object]:
     """MLM_PLL/main.py:117-161 (mlm_finetune_bert) on the native trainer (``train.MLMTrainer``).
 
@@ -316,7 +350,8 @@ def mlm_finetune(cfg) -> Dict[str, object]:
     ``train.mask_tokens`` (BERT's 80/10/10 at ``mlm_probability``, default 0.15) seeded by
     ``(seed, epoch)`` and the batch index; the dev loss uses the masks of ``(seed, 0)`` at every
     epoch, so epochs compare; ``mlm_whole_word: true`` selects whole words and needs ``model.vocab``.
-    Checkpoints and ``loss.json`` are the same in every mode."""
+    Checkpoints and ``loss.json`` are the same in every mode.  Optimizer options: ``accum_steps``,
+    ``max_grad_norm``, ``lr_schedule`` / ``warmup_steps``, ``freeze`` (``_optim_plan``)."""
     import torch
     from .train import MLMTrainer, do_job_rows, mlm_epoch, mlm_epoch_dynamic
     os.makedirs(cfg.output_path, exist_ok=True)
@@ -388,11 +423,11 @@ def mlm_finetune(cfg) -> Dict[str, object]:
     ignore = -100 if lab_mode == "masked" else None
     seed = int(get(cfg, "seed", 0))
 
-    def epoch_pass(d, ep, update, order=None):
+    def epoch_pass(d, ep, update, order=None, **kw):
         if masking == "dynamic":
             return mlm_epoch_dynamic(tr, d[0], bs, (seed, ep), update=update, order=order, mlm_probability=prob,
-                                     continuation=d[1])
-        return mlm_epoch(tr, *d, bs, update=update, order=order, ignore_index=ignore)
+                                     continuation=d[1], **kw)
+        return mlm_epoch(tr, *d, bs, update=update, order=order, ignore_index=ignore, **kw)
     tr = MLMTrainer(_weights(cfg, "mlm"), BERT_BASE, device=_dev(cfg), lr=float(get(cfg, "lr", 1e-5)),
                     weight_decay=float(get(cfg, "weight_decay", 0.01)), **_dropout_args(cfg))
     bs = int(get(cfg, "dataloader.batch_size", get(cfg, "batch_size", 32)))
@@ -401,11 +436,12 @@ def mlm_finetune(cfg) -> Dict[str, object]:
     epochs = int(get(cfg, "epoch", 1))
     train_rec, dev_rec, ckpts = [0] * epochs, [0] * epochs, []
     try:
+        optim = _optim_plan(cfg, tr, -(-len(train_d[0]) // bs), epochs)
         for ep in range(1, epochs + 1):
             tr.reset_optimizer()
             tr.set_dropout_step(ep << 32)            # epoch-keyed masks: a resumed run draws the same
             order = torch.randperm(len(train_d[0]), generator=gen).numpy() if shuffle else None
-            train_rec[ep - 1] = epoch_pass(train_d, ep, True, order)
+            train_rec[ep - 1] = epoch_pass(train_d, ep, True, order, **optim(ep))
             print("epoch ", ep, " train loss: ", train_rec[ep - 1])
             if dev_d is not None:
                 dev_rec[ep - 1] = epoch_pass(dev_d, 0, "loss")
@@ -494,7 +530,8 @@ def rescorebert_train(cfg) -> Dict[str, object]:
     ``dev_context_text_path`` (context pairs with segment ids).  Per epoch: a fresh
     AdamW (``:83-86``), the train pass, the dev loss (no update), ``checkpoint_{epoch}.pth``
     and ``loss.json``.  Extra: ``checkpoint_path`` / ``random_init_seed`` (initial weights:
-    bert-base-chinese cannot be fetched offline), ``weight_decay``, dropout keys (``_dropout_args``)."""
+    bert-base-chinese cannot be fetched offline), ``weight_decay``, dropout keys (``_dropout_args``),
+    ``accum_steps``, ``max_grad_norm``, ``lr_schedule`` / ``warmup_steps``, ``freeze`` (``_optim_plan``)."""
     from .train import RescoreBertTrainer, rescorebert_epoch
     os.makedirs(cfg.output_path, exist_ok=True)
     method = str(get(cfg, "method", "MD"))
@@ -517,17 +554,19 @@ def rescorebert_train(cfg) -> Dict[str, object]:
                             weight_decay=float(get(cfg, "weight_decay", 0.01)), **_dropout_args(cfg))
     bs, n_best = int(get(cfg, "batch_size", 1)), int(get(cfg, "n_best", 1))
 
-    def epoch_pass(f, update):
+    def epoch_pass(f, update, **kw):
         z = np.zeros(len(f["hyp_off"]) - 1, np.float32)
         return rescorebert_epoch(tr, f["tokens"], f["hyp_off"], f["mlm_pll_score"], f.get("hyps_am_score", z),
-                                 f.get("hyps_cer", z), bs, n_best, update=update, token_types=f.get("token_type"))
+                                 f.get("hyps_cer", z), bs, n_best, update=update, token_types=f.get("token_type"),
+                                 **kw)
     ckpts = []
     try:
+        optim = _optim_plan(cfg, tr, -(-(len(train_f["hyp_off"]) - 1) // (bs * n_best)), int(get(cfg, "epoch", 1)))
         for ep in range(int(start) if resume else 1, int(get(cfg, "epoch", 1)) + 1):
             print("Epoch {}/{}".format(ep, get(cfg, "epoch", 1)))
             tr.reset_optimizer()
             tr.set_dropout_step(ep << 32)            # epoch-keyed masks: a resumed run draws the same
-            train_rec.append(epoch_pass(train_f, True))
+            train_rec.append(epoch_pass(train_f, True, **optim(ep)))
             print("epoch ", ep, " train loss: ", train_rec[-1], "\n")
             if dev_f is not None and all(f in dev_f["features"] for f in need):
                 dev_rec.append(epoch_pass(dev_f, "loss"))

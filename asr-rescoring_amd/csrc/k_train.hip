@@ -949,6 +949,99 @@ __global__ void tr_adamw4_kernel(float4* __restrict__ p, const float4* __restric
     }
 }
 
+// The AdamW step on a scaled gradient gmul * g (rs_trainer_apply: gradient accumulation's 1/k and
+// the clip_grad_norm_ coefficient, folded into one float on the host).  The product is rounded once
+// to fp32 before the update, as torch's in-place g.mul_(c) leaves it (__fmul_rn: never contracted
+// into adamw1's g - m, so the float4 and scalar forms agree bit for bit as the unscaled pair does).
+__global__ void tr_adamw_scaled_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                       float* __restrict__ v, long long n, float gmul, float decay, float b1w,
+                                       float b2, float b2w, float step_size, float bc2_sqrt, float eps) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        float pi = p[i], mi = m[i], vi = v[i];
+        adamw1(pi, __fmul_rn(gmul, g[i]), mi, vi, decay, b1w, b2, b2w, step_size, bc2_sqrt, eps);
+        m[i] = mi;
+        v[i] = vi;
+        p[i] = pi;
+    }
+}
+
+__global__ void tr_adamw4_scaled_kernel(float4* __restrict__ p, const float4* __restrict__ g, float4* __restrict__ m,
+                                        float4* __restrict__ v, long long n4, float gmul, float decay, float b1w,
+                                        float b2, float b2w, float step_size, float bc2_sqrt, float eps) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+        float4 pi = p[i], mi = m[i], vi = v[i];
+        const float4 gi = g[i];
+        adamw1(pi.x, __fmul_rn(gmul, gi.x), mi.x, vi.x, decay, b1w, b2, b2w, step_size, bc2_sqrt, eps);
+        adamw1(pi.y, __fmul_rn(gmul, gi.y), mi.y, vi.y, decay, b1w, b2, b2w, step_size, bc2_sqrt, eps);
+        adamw1(pi.z, __fmul_rn(gmul, gi.z), mi.z, vi.z, decay, b1w, b2, b2w, step_size, bc2_sqrt, eps);
+        adamw1(pi.w, __fmul_rn(gmul, gi.w), mi.w, vi.w, decay, b1w, b2, b2w, step_size, bc2_sqrt, eps);
+        m[i] = mi;
+        v[i] = vi;
+        p[i] = pi;
+    }
+}
+
+// Gradient accumulation (rs_trainer_accumulate): acc = fmaf(w, g, acc), one rounding per element
+// per micro-batch, in the order of the calls.  Scalar and float4 forms, the same arithmetic.
+__global__ void tr_accum_kernel(float* __restrict__ acc, const float* __restrict__ g, long long n, float w) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+        acc[i] = fmaf(w, g[i], acc[i]);
+}
+
+__global__ void tr_accum4_kernel(float4* __restrict__ acc, const float4* __restrict__ g, long long n4, float w) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+        float4 a = acc[i];
+        const float4 gi = g[i];
+        a.x = fmaf(w, gi.x, a.x);
+        a.y = fmaf(w, gi.y, a.y);
+        a.z = fmaf(w, gi.z, a.z);
+        a.w = fmaf(w, gi.w, a.w);
+        acc[i] = a;
+    }
+}
+
+// Sum of squares in float64 (the gradient norm of rs_trainer_grad_norm / rs_trainer_apply), ordered:
+// the grid is a function of n alone (at most kSumsqBlocks blocks of 256 threads), thread t of the
+// grid sums the squares of its strided share in index order (an fp32 square is exact in float64),
+// a wave adds its 64 lanes by a fixed xor butterfly, thread 0 adds the block's 4 waves in wave
+// order and writes the block's partial; tr_sumsq_final_kernel adds the partials of all ranges in
+// index order.  No atomics: the same buffer gives the same bits on every run and every device.
+constexpr int kSumsqBlocks = 512;
+
+template <bool VEC>
+__global__ void __launch_bounds__(256)
+tr_sumsq_kernel(const float* __restrict__ g, long long n, double* __restrict__ part) {
+    __shared__ double sh[4];
+    const long long gt = blockIdx.x * 256LL + threadIdx.x, stride = gridDim.x * 256LL;
+    double acc = 0.0;
+    long long i0 = gt;
+    if (VEC) {
+        const long long n4 = n / 4;
+        const float4* g4 = (const float4*)g;
+        for (long long i = gt; i < n4; i += stride) {
+            const float4 x = g4[i];
+            acc += (double)x.x * (double)x.x;
+            acc += (double)x.y * (double)x.y;
+            acc += (double)x.z * (double)x.z;
+            acc += (double)x.w * (double)x.w;
+        }
+        i0 = n4 * 4 + gt;                       // the n % 4 tail
+    }
+    for (long long i = i0; i < n; i += stride) acc += (double)g[i] * (double)g[i];
+    for (int d = 32; d > 0; d >>= 1) acc += __shfl_xor(acc, d, 64);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+}
+
+__global__ void tr_sumsq_final_kernel(const double* __restrict__ part, int n_part, double* __restrict__ out) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        double s = 0.0;
+        for (int i = 0; i < n_part; ++i) s += part[i];
+        out[0] = s;
+    }
+}
+
 __global__ void tr_dropout_kernel(float* dst, const float* src, long long n, TrDrop dr) {
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
         dst[i] = tr_drop(dr, (unsigned long long)i, src[i]);
@@ -1266,6 +1359,59 @@ hipError_t tr_adamw(float* p, const float* g, float* m, float* v, long long n, f
     return hipGetLastError();
 }
 
+hipError_t tr_adamw_scaled(float* p, const float* g, float* m, float* v, long long n, float gmul, float decay,
+                           float b1w, float b2, float b2w, float step_size, float bc2_sqrt, float eps, hipStream_t s) {
+    if (gmul == 1.0f) return tr_adamw(p, g, m, v, n, decay, b1w, b2, b2w, step_size, bc2_sqrt, eps, s);
+    if (n <= 0) return hipSuccess;
+    if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0 && n >= 4) {
+        const long long n4 = n / 4, done = n4 * 4;
+        hipLaunchKernelGGL(tr_adamw4_scaled_kernel, dim3(grid_for(n4, 256)), dim3(256), 0, s, (float4*)p,
+                           (const float4*)g, (float4*)m, (float4*)v, n4, gmul, decay, b1w, b2, b2w, step_size,
+                           bc2_sqrt, eps);
+        if (done < n)
+            hipLaunchKernelGGL(tr_adamw_scaled_kernel, dim3(1), dim3(64), 0, s, p + done, g + done, m + done, v + done,
+                               n - done, gmul, decay, b1w, b2, b2w, step_size, bc2_sqrt, eps);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(tr_adamw_scaled_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, p, g, m, v, n, gmul, decay, b1w,
+                       b2, b2w, step_size, bc2_sqrt, eps);
+    return hipGetLastError();
+}
+
+hipError_t tr_accum(float* acc, const float* g, long long n, float w, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    if ((((uintptr_t)acc | (uintptr_t)g) & 15) == 0 && n >= 4) {
+        const long long n4 = n / 4, done = n4 * 4;
+        hipLaunchKernelGGL(tr_accum4_kernel, dim3(grid_for(n4, 256)), dim3(256), 0, s, (float4*)acc, (const float4*)g,
+                           n4, w);
+        if (done < n)
+            hipLaunchKernelGGL(tr_accum_kernel, dim3(1), dim3(64), 0, s, acc + done, g + done, n - done, w);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(tr_accum_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, acc, g, n, w);
+    return hipGetLastError();
+}
+
+size_t tr_sumsq_ws_doubles(int n_ranges) { return 1 + (size_t)std::max(n_ranges, 0) * kSumsqBlocks; }
+
+hipError_t tr_sumsq(const float* base, const TrRange* r, int n_ranges, double* ws, hipStream_t s) {
+    int n_part = 0;
+    for (int k = 0; k < n_ranges; ++k) {
+        if (r[k].n <= 0) continue;
+        const float* g = base + r[k].off;
+        const bool vec = ((uintptr_t)g & 15) == 0 && r[k].n >= 4;
+        const long long items = vec ? r[k].n / 4 : r[k].n;
+        const int nb = (int)std::min<long long>((items + 255) / 256, kSumsqBlocks);
+        if (vec)
+            hipLaunchKernelGGL(tr_sumsq_kernel<true>, dim3(nb), dim3(256), 0, s, g, r[k].n, ws + 1 + n_part);
+        else
+            hipLaunchKernelGGL(tr_sumsq_kernel<false>, dim3(nb), dim3(256), 0, s, g, r[k].n, ws + 1 + n_part);
+        n_part += nb;
+    }
+    hipLaunchKernelGGL(tr_sumsq_final_kernel, dim3(1), dim3(64), 0, s, ws + 1, n_part, ws);
+    return hipGetLastError();
+}
+
 hipError_t tr_dropout(float* dst, const float* src, long long n, const TrDrop& d, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(tr_dropout_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, dst, src, n, d);
@@ -1524,4 +1670,65 @@ extern "C" int rs_debug_train_adamw(float* p, const float* g, float* m, float* v
     const TrAdamW a = tr_adamw_scalars(lr, beta1, beta2, eps, weight_decay, step);
     return dbg_done(tr_adamw(p, g, m, v, n, a.decay, a.b1w, a.b2, a.b2w, a.step_size, a.bc2_sqrt, a.eps, s), s,
                     "rs_debug_train_adamw");
+}
+
+// The same step on the scaled gradient gmul * g (tr_adamw_scaled, what rs_trainer_apply launches)
+extern "C" int rs_debug_train_adamw_scaled(float* p, const float* g, float* m, float* v, long long n, float gmul,
+                                           float lr, float beta1, float beta2, float eps, float weight_decay,
+                                           long long step, void* stream) {
+    if (!p || !g || !m || !v) return rs_fail(RS_EARG, "null argument");
+    if (n <= 0 || step < 1) return rs_fail(RS_EARG, "n and step must be positive");
+    hipStream_t s = (hipStream_t)stream;
+    const TrAdamW a = tr_adamw_scalars(lr, beta1, beta2, eps, weight_decay, step);
+    return dbg_done(tr_adamw_scaled(p, g, m, v, n, gmul, a.decay, a.b1w, a.b2, a.b2w, a.step_size, a.bc2_sqrt, a.eps, s),
+                    s, "rs_debug_train_adamw_scaled");
+}
+
+namespace {
+
+// a host range list (offset, count) inside a buffer of n_total floats
+int dbg_ranges(const long long* h_off, const long long* h_n, int n_ranges, long long n_total, std::vector<TrRange>& r) {
+    if (!h_off || !h_n || n_ranges <= 0) return rs_fail(RS_EARG, "null / empty range list");
+    for (int k = 0; k < n_ranges; ++k) {
+        if (h_off[k] < 0 || h_n[k] <= 0 || h_off[k] > n_total || h_n[k] > n_total - h_off[k])
+            return rs_fail(RS_EARG, "range " + std::to_string(k) + " outside the buffer");
+        r.push_back({h_off[k], h_n[k]});
+    }
+    return RS_OK;
+}
+
+}  // namespace
+
+// acc[i] = fmaf(w, g[i], acc[i]) over the listed ranges of acc, g [n_total] (tr_accum per range, as
+// rs_trainer_accumulate runs it); everything outside the ranges is left alone
+extern "C" int rs_debug_train_accum(float* acc, const float* g, const long long* h_off, const long long* h_n,
+                                    int n_ranges, long long n_total, float w, void* stream) {
+    if (!acc || !g) return rs_fail(RS_EARG, "null argument");
+    std::vector<TrRange> r;
+    if (int e = dbg_ranges(h_off, h_n, n_ranges, n_total, r)) return e;
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = hipSuccess;
+    for (const TrRange& x : r)
+        if (e == hipSuccess) e = tr_accum(acc + x.off, g + x.off, x.n, w, s);
+    return dbg_done(e, s, "rs_debug_train_accum");
+}
+
+// h_out[0] = float64 sum of squares of g [n_total] over the listed ranges (tr_sumsq; its square root
+// is the norm rs_trainer_grad_norm returns)
+extern "C" int rs_debug_train_sumsq(const float* g, const long long* h_off, const long long* h_n, int n_ranges,
+                                    long long n_total, double* h_out, void* stream) {
+    if (!g || !h_out) return rs_fail(RS_EARG, "null argument");
+    std::vector<TrRange> r;
+    if (int e = dbg_ranges(h_off, h_n, n_ranges, n_total, r)) return e;
+    hipStream_t s = (hipStream_t)stream;
+    double* ws = nullptr;
+    if (hipMalloc((void**)&ws, tr_sumsq_ws_doubles(n_ranges) * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        return rs_fail(RS_ENOMEM, "rs_debug_train_sumsq: scratch");
+    }
+    hipError_t e = tr_sumsq(g, r.data(), n_ranges, ws, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(h_out, ws, 8, hipMemcpyDeviceToHost, s);
+    const int rc = dbg_done(e, s, "rs_debug_train_sumsq");
+    (void)hipFree(ws);
+    return rc;
 }

@@ -113,6 +113,19 @@ hipError_t tr_gather_rows(const float* src, const int* rows, int n, int H, float
 hipError_t tr_expand_rows(const float* src, const int* inv, int M, int H, float* dst, hipStream_t s);
 hipError_t tr_adamw(float* p, const float* g, float* m, float* v, long long n, float decay, float b1w, float b2,
                     float b2w, float step_size, float bc2_sqrt, float eps, hipStream_t s);
+// The same step on the gradient gmul * g, the product rounded once to fp32 (rs_trainer_apply's
+// accumulation scale and clip coefficient); gmul == 1: tr_adamw itself.
+hipError_t tr_adamw_scaled(float* p, const float* g, float* m, float* v, long long n, float gmul, float decay,
+                           float b1w, float b2, float b2w, float step_size, float bc2_sqrt, float eps, hipStream_t s);
+// acc[i] = fmaf(w, g[i], acc[i]), i < n (gradient accumulation)
+hipError_t tr_accum(float* acc, const float* g, long long n, float w, hipStream_t s);
+// ws[0] = float64 sum of g[i]^2 over the ranges [off, off + n) of base, ordered and atomics-free
+// (the same bits on every run); ws: tr_sumsq_ws_doubles(n_ranges) doubles
+struct TrRange {
+    long long off, n;
+};
+size_t tr_sumsq_ws_doubles(int n_ranges);
+hipError_t tr_sumsq(const float* base, const TrRange* r, int n_ranges, double* ws, hipStream_t s);
 // tr_adamw's scalars for optimizer step `step` (1-based) of torch.optim.AdamW: python-float
 // (double) scalars as torch computes them, cast to the fp32 tensor dtype
 struct TrAdamW {

@@ -9,12 +9,16 @@
 // the three HF tensors.  GEMMs: tr_sgemm (k_sgemm.hip: f32-input MFMA, exact fp32, split-K
 // through an ordered workspace sum — deterministic); RS_TRAIN_ROCBLAS=1 routes them to rocBLAS
 // sgemm instead (atomics disabled), kept as the timing / numerics baseline.
+// Optimizer options (rs_trainer_accumulate / _apply / _grad_norm / _set_trainable): gradient
+// accumulation, clip_grad_norm_ and frozen tensors are range arithmetic over those flat buffers; a
+// step that uses none of them launches what it always did.
 // All other ops: k_train.hip.  Dropout (BERT's train mode, train.h TrDrop): hidden dropout after
 // the embedding LayerNorm and on both residual branches, attention-probability dropout; the keep
 // bits are counter-based draws keyed by (dropout_seed, the trainer's dropout-step counter), so a
 // step is bitwise reproducible and the backward recomputes the mask.
 #include <algorithm>
 #include <map>
+#include <set>
 #include <string>
 #include <vector>
 #include <cstring>
@@ -66,6 +70,15 @@ struct rs_trainer {
     // rs_trainer_set_token_types: segment ids of the next step, [type_n] device ints (null: all 0)
     const int32_t* type_next = nullptr;
     int64_t type_n = 0;
+    // Frozen tensors (rs_trainer_set_trainable): their offsets, and the maximal merged ranges of the
+    // trainable ones (64-float aligned; one range [0, n_params) while nothing is frozen) that AdamW,
+    // the gradient norm and the accumulation run over
+    std::set<size_t> frozen;
+    std::vector<TrRange> ranges;
+    DevBuf A, nws;             // gradient accumulator (allocated at the first rs_trainer_accumulate); norm partials
+    bool have_grad = false;    // t->G holds the gradient of a completed backward under the current trainable set
+    bool acc_filled = false;   // a micro-batch has been accumulated since the last clear
+    bool on(size_t off) const { return !frozen.count(off); }
 };
 
 namespace {
@@ -75,6 +88,21 @@ size_t add_tensor(rs_trainer* t, const std::string& key, size_t n) {
     t->table[key] = {off, n};
     t->n_params = off + n;
     return off;
+}
+
+// the maximal merged ranges of the trainable tensors, each tensor padded to its 64-float slot
+void merge_ranges(rs_trainer* t) {
+    std::map<size_t, size_t> by_off;                          // offset -> numel
+    for (auto& kv : t->table) by_off[kv.second.first] = kv.second.second;
+    t->ranges.clear();
+    for (auto& on : by_off) {
+        if (t->frozen.count(on.first)) continue;
+        const long long b = (long long)on.first, e = (long long)((on.first + on.second + 63) / 64 * 64);
+        if (!t->ranges.empty() && t->ranges.back().off + t->ranges.back().n == b)
+            t->ranges.back().n = e - t->ranges.back().off;
+        else
+            t->ranges.push_back({b, e - b});
+    }
 }
 
 // rocBLAS baseline (RS_TRAIN_ROCBLAS=1): the same three forms, column-major arguments
@@ -204,6 +232,7 @@ int rs_trainer_create(const rs_bert_cfg* cfg, int device, rs_trainer** out) {
     t->n_params = (t->n_params + 63) / 64 * 64;
     t->host.assign(t->n_params, 0.0f);
     t->set.assign(t->table.size(), 0);
+    merge_ranges(t);
     *out = t;
     return RS_OK;
 }
@@ -272,8 +301,24 @@ int rs_trainer_get_tensor(rs_trainer* t, const char* key, void* host_out, int64_
     return copy_out(t, t ? t->P : DevBuf{}, key, host_out, numel);
 }
 
+// torch's .grad of a requires_grad = False tensor is None
+static int check_not_frozen(rs_trainer* t, const char* key) {
+    if (!t || !key) return RS_OK;                // copy_out reports it
+    auto it = t->table.find(key);
+    if (it != t->table.end() && !t->on(it->second.first))
+        return rs_fail(RS_ESTATE, std::string("tensor ") + key + " is frozen: it has no gradient");
+    return RS_OK;
+}
+
 int rs_trainer_get_grad(rs_trainer* t, const char* key, void* host_out, int64_t numel) {
+    if (int r = check_not_frozen(t, key)) return r;
     return copy_out(t, t ? t->G : DevBuf{}, key, host_out, numel);
+}
+
+int rs_trainer_get_accum(rs_trainer* t, const char* key, void* host_out, int64_t numel) {
+    if (int r = check_not_frozen(t, key)) return r;
+    if (t && !t->acc_filled) return rs_fail(RS_ESTATE, "the accumulator is empty");
+    return copy_out(t, t ? t->A : DevBuf{}, key, host_out, numel);
 }
 
 }  // extern "C"
@@ -566,8 +611,36 @@ int encoder_forward(StepCtx& c) {
     return RS_OK;
 }
 
+// What of the encoder's backward the trainable set asks for (rs_trainer_set_trainable): emb, any
+// embedding tensor trainable; lo, the lowest layer with a trainable tensor (layers: none).  Layers
+// below lo launch nothing unless the embeddings need the gradient carried down to them.
+struct BwdPlan {
+    bool emb = true;
+    int lo = 0, n_layers = 0;
+    bool any() const { return emb || lo < n_layers; }
+};
+BwdPlan bwd_plan(const rs_trainer* t) {
+    BwdPlan p;
+    p.n_layers = t->cfg.layers;
+    if (t->frozen.empty()) return p;
+    p.emb = t->on(t->o_word) || t->on(t->o_pos) || t->on(t->o_type) || t->on(t->o_eg) || t->on(t->o_eb);
+    const size_t HH = (size_t)t->cfg.hidden * t->cfg.hidden, H = t->cfg.hidden;
+    for (p.lo = 0; p.lo < p.n_layers; ++p.lo) {
+        const TLayer& L = t->lay[p.lo];
+        bool any = false;
+        for (size_t o : {L.wqkv, L.wqkv + HH, L.wqkv + 2 * HH, L.bqkv, L.bqkv + H, L.bqkv + 2 * H, L.wo, L.bo, L.g1,
+                         L.be1, L.w1, L.b1, L.w2, L.b2, L.g2, L.be2})
+            any = any || t->on(o);
+        if (any) break;
+    }
+    return p;
+}
+
 // from dA = d(final hidden) down to the embeddings; gradients written into t->G (zeroed by
-// the caller before the head's backward)
+// the caller before the head's backward).  The weight / bias / LayerNorm gradient of a frozen tensor
+// is not launched (the fused Q|K|V pair runs while any of its three is trainable; a LayerNorm's
+// gamma / beta pair while either is), and the chain stops where nothing below is trainable.  With
+// nothing frozen every condition is true: the launches of the unpruned backward, in its order.
 int encoder_backward(StepCtx& c) {
     rs_trainer* t = c.t;
     const rs_bert_cfg& cf = t->cfg;
@@ -576,10 +649,13 @@ int encoder_backward(StepCtx& c) {
     float *Pm = t->P.as<float>(), *Gm = t->G.as<float>();
     float *dA = c.dA, *dB = c.dB, *dF = c.dF, *dQKV = c.dQKV, *part = c.part;
     hipStream_t st = c.st;
-    for (int l = cf.layers - 1; l >= 0; --l) {
+    const BwdPlan plan = bwd_plan(t);
+    const size_t HH = (size_t)H * H;
+    auto on = [t](size_t off) { return t->on(off); };
+    for (int l = cf.layers - 1; l >= (plan.emb ? 0 : plan.lo); --l) {
         const TLayer& L = t->lay[l];
         StepCtx::LA& a = c.la[l];
-        TRY_HIP(tr_colsum_ln(dA, a.x2, a.st2, M, H, part, Gm + L.g2, Gm + L.be2, st));
+        if (on(L.g2) || on(L.be2)) TRY_HIP(tr_colsum_ln(dA, a.x2, a.st2, M, H, part, Gm + L.g2, Gm + L.be2, st));
         TRY_HIP(tr_ln_bwd(dA, a.x2, a.st2, Pm + L.g2, dB, M, H, st));              // dB = dx2
         // BertOutput dropout: the dense branch sees dx2 * mask * scale (in the free dQKV
         // buffer), the residual branch dx2 itself (dB, copied into dA below)
@@ -588,15 +664,15 @@ int encoder_backward(StepCtx& c) {
             TRY_HIP(tr_dropout(dQKV, dB, (long long)MH, c.drop(3 + 3 * l, false), st));
             dBo = dQKV;
         }
-        TRY_HIP(tr_colsum(dBo, nullptr, nullptr, M, H, 0, part, Gm + L.b2, 0, st));
-        RS_TRY(gemm_tn(t, st, M, H, F, dBo, a.act, Gm + L.w2, 0.f));
+        if (on(L.b2)) TRY_HIP(tr_colsum(dBo, nullptr, nullptr, M, H, 0, part, Gm + L.b2, 0, st));
+        if (on(L.w2)) RS_TRY(gemm_tn(t, st, M, H, F, dBo, a.act, Gm + L.w2, 0.f));
         RS_TRY(gemm_nn(t, st, M, H, F, dBo, Pm + L.w2, dF, 0.f));                   // d act
         TRY_HIP(tr_gelu_bwd(dF, a.pre, (long long)MF, st));                         // d pre
-        TRY_HIP(tr_colsum(dF, nullptr, nullptr, M, F, 0, part, Gm + L.b1, 0, st));
-        RS_TRY(gemm_tn(t, st, M, F, H, dF, a.h1, Gm + L.w1, 0.f));
+        if (on(L.b1)) TRY_HIP(tr_colsum(dF, nullptr, nullptr, M, F, 0, part, Gm + L.b1, 0, st));
+        if (on(L.w1)) RS_TRY(gemm_tn(t, st, M, F, H, dF, a.h1, Gm + L.w1, 0.f));
         TRY_HIP(hipMemcpyAsync(dA, dB, MH * 4, hipMemcpyDeviceToDevice, st));      // residual
         RS_TRY(gemm_nn(t, st, M, F, H, dF, Pm + L.w1, dA, 1.f));                     // dA = d h1
-        TRY_HIP(tr_colsum_ln(dA, a.x1, a.st1, M, H, part, Gm + L.g1, Gm + L.be1, st));
+        if (on(L.g1) || on(L.be1)) TRY_HIP(tr_colsum_ln(dA, a.x1, a.st1, M, H, part, Gm + L.g1, Gm + L.be1, st));
         TRY_HIP(tr_ln_bwd(dA, a.x1, a.st1, Pm + L.g1, dB, M, H, st));              // dB = dx1
         // BertSelfOutput dropout: masked copy for the dense branch in the free dF buffer
         const float* dBs = dB;
@@ -604,26 +680,34 @@ int encoder_backward(StepCtx& c) {
             TRY_HIP(tr_dropout(dF, dB, (long long)MH, c.drop(2 + 3 * l, false), st));
             dBs = dF;
         }
-        TRY_HIP(tr_colsum(dBs, nullptr, nullptr, M, H, 0, part, Gm + L.bo, 0, st));
-        RS_TRY(gemm_tn(t, st, M, H, H, dBs, a.ctx, Gm + L.wo, 0.f));
+        if (on(L.bo)) TRY_HIP(tr_colsum(dBs, nullptr, nullptr, M, H, 0, part, Gm + L.bo, 0, st));
+        if (on(L.wo)) RS_TRY(gemm_tn(t, st, M, H, H, dBs, a.ctx, Gm + L.wo, 0.f));
         RS_TRY(gemm_nn(t, st, M, H, H, dBs, Pm + L.wo, dA, 0.f));                    // dA = d ctx
         if (c.tiled)
             TRY_HIP(tr_attn_bwd_tiled(a.qkv, a.P, dA, c.seq, c.pofs, c.S, c.tmax, H, nh, c.dS, dQKV, st,
                                       c.drop(1 + 3 * l, true)));
         else
             TRY_HIP(tr_attn_bwd(a.qkv, a.P, dA, c.seq, c.pofs, c.S, c.tmax, H, nh, dQKV, st, c.drop(1 + 3 * l, true)));
-        TRY_HIP(tr_colsum(dQKV, nullptr, nullptr, M, 3 * H, 0, part, Gm + L.bqkv, 0, st));
-        RS_TRY(gemm_tn(t, st, M, 3 * H, H, dQKV, a.hin, Gm + L.wqkv, 0.f));
+        if (on(L.bqkv) || on(L.bqkv + H) || on(L.bqkv + 2 * H))
+            TRY_HIP(tr_colsum(dQKV, nullptr, nullptr, M, 3 * H, 0, part, Gm + L.bqkv, 0, st));
+        if (on(L.wqkv) || on(L.wqkv + HH) || on(L.wqkv + 2 * HH))
+            RS_TRY(gemm_tn(t, st, M, 3 * H, H, dQKV, a.hin, Gm + L.wqkv, 0.f));
+        if (!plan.emb && l == plan.lo) break;           // nothing below takes the layer's input gradient
         TRY_HIP(hipMemcpyAsync(dA, dB, MH * 4, hipMemcpyDeviceToDevice, st));      // residual
         RS_TRY(gemm_nn(t, st, M, 3 * H, H, dQKV, Pm + L.wqkv, dA, 1.f));             // dA = d h_in
     }
+    if (!plan.emb) return RS_OK;
     // embedding dropout: d(LN output) = d h0 * mask * scale
     if (c.th_hidden) TRY_HIP(tr_dropout(dA, dA, (long long)MH, c.drop(0, false), st));
-    TRY_HIP(tr_colsum_ln(dA, c.x0, c.st0, M, H, part, Gm + t->o_eg, Gm + t->o_eb, st));
+    if (on(t->o_eg) || on(t->o_eb))
+        TRY_HIP(tr_colsum_ln(dA, c.x0, c.st0, M, H, part, Gm + t->o_eg, Gm + t->o_eb, st));
+    if (!(on(t->o_word) || on(t->o_pos) || on(t->o_type))) return RS_OK;
     TRY_HIP(tr_ln_bwd(dA, c.x0, c.st0, Pm + t->o_eg, dB, M, H, st));                // dB = dx0
     // word embeddings: += (the tied MLM decoder already wrote its part)
-    TRY_HIP(tr_word_grad(dB, c.dm + c.i_utok, c.dm + c.i_toff, c.dm + c.i_ord, c.n_uniq, H, Gm + t->o_word, st));
-    TRY_HIP(tr_pos_grad(dB, c.seq, c.S, c.tmax, H, Gm + t->o_pos, st));
+    if (on(t->o_word))
+        TRY_HIP(tr_word_grad(dB, c.dm + c.i_utok, c.dm + c.i_toff, c.dm + c.i_ord, c.n_uniq, H, Gm + t->o_word, st));
+    if (on(t->o_pos)) TRY_HIP(tr_pos_grad(dB, c.seq, c.S, c.tmax, H, Gm + t->o_pos, st));
+    if (!on(t->o_type)) return RS_OK;
     // token types: without segment ids every row into row 0 (the other rows stay 0 from the step's
     // memset); with them, row k from the rows of type k, one predicated pass per type
     if (!c.row_type())
@@ -634,12 +718,28 @@ int encoder_backward(StepCtx& c) {
     return RS_OK;
 }
 
-int adamw(rs_trainer* t, const rs_train_opts* o, hipStream_t st) {
-    if (o->update != 1) return RS_OK;
+// one AdamW step (number t->step + 1) on the gradient gmul * src over the trainable ranges: a frozen
+// tensor keeps its parameter and its moments (no decay).  Nothing frozen and gmul == 1: the one
+// tr_adamw launch over the whole flat vector.
+int adamw_ranges(rs_trainer* t, const rs_train_opts* o, const float* src, float gmul, hipStream_t st) {
     t->step += 1;
     const TrAdamW a = tr_adamw_scalars(o->lr, o->beta1, o->beta2, o->eps, o->weight_decay, t->step);
-    TRY_HIP(tr_adamw(t->P.as<float>(), t->G.as<float>(), t->M1.as<float>(), t->V1.as<float>(), (long long)t->n_params,
-                     a.decay, a.b1w, a.b2, a.b2w, a.step_size, a.bc2_sqrt, a.eps, st));
+    for (const TrRange& r : t->ranges)
+        TRY_HIP(tr_adamw_scaled(t->P.as<float>() + r.off, src + r.off, t->M1.as<float>() + r.off,
+                                t->V1.as<float>() + r.off, r.n, gmul, a.decay, a.b1w, a.b2, a.b2w, a.step_size,
+                                a.bc2_sqrt, a.eps, st));
+    return RS_OK;
+}
+
+int adamw(rs_trainer* t, const rs_train_opts* o, hipStream_t st) {
+    if (o->update != 1) return RS_OK;
+    return adamw_ranges(t, o, t->G.as<float>(), 1.0f, st);
+}
+
+// a step that runs a backward (update >= 0) needs something to train; raised before any state moves
+int check_trainable(const rs_trainer* t, const rs_train_opts* o) {
+    if (o->update >= 0 && t->ranges.empty())
+        return rs_fail(RS_ESTATE, "every tensor is frozen (rs_trainer_set_trainable): nothing to compute a gradient for");
     return RS_OK;
 }
 
@@ -660,6 +760,7 @@ int rs_train_step_cls(rs_trainer* t, const int32_t* d_tok, const int32_t* h_hyp_
     if (h_utt_off[0] != 0 || h_utt_off[n_utt] != n_hyp) return rs_fail(RS_EARG, "utt_off must span 0..n_hyp");
     for (int u = 0; u < n_utt; ++u)
         if (h_utt_off[u + 1] < h_utt_off[u]) return rs_fail(RS_EARG, "utt_off not ascending");
+    if (int r = check_trainable(t, o)) return r;
     StepCtx c;
     c.t = t;
     c.st = (hipStream_t)stream;
@@ -681,6 +782,7 @@ int rs_train_step_cls(rs_trainer* t, const int32_t* d_tok, const int32_t* h_hyp_
         TRY_HIP(hipStreamSynchronize(st));
         return RS_OK;
     }
+    t->have_grad = false;
     TRY_HIP(hipMemsetAsync(Gm, 0, t->n_params * 4, st));
     TRY_HIP(hipMemsetAsync(c.dA, 0, (size_t)c.M * H * 4, st));
     TRY_HIP(tr_cls_bwd(dsc, hfin, c.seq, S, H, Pm + t->o_wl, c.dA, Gm + t->o_wl, Gm + t->o_bl, st));
@@ -688,6 +790,7 @@ int rs_train_step_cls(rs_trainer* t, const int32_t* d_tok, const int32_t* h_hyp_
     if (int r = adamw(t, o, st)) return r;
     TRY_HIP(hipStreamSynchronize(st));        // the metadata upload read t->h_meta
     if (tr_sgemm_failed()) return rs_fail(RS_EHIP, "a stream-K GEMM timed out waiting for a partial tile");
+    t->have_grad = true;
     return RS_OK;
 }
 
@@ -698,6 +801,7 @@ int rs_train_step_cls(rs_trainer* t, const int32_t* d_tok, const int32_t* h_hyp_
 static int mlm_step(rs_trainer* t, const TypeStep& ty, const int32_t* d_ids, const int32_t* h_seq_off, int32_t n_seq,
                     const int32_t* h_key_len, const int32_t* h_lab, int32_t n_lab, const int32_t* d_labels,
                     const rs_train_opts* o, float* d_loss, void* stream) {
+    if (int r = check_trainable(t, o)) return r;
     StepCtx c;
     c.t = t;
     c.st = (hipStream_t)stream;
@@ -725,18 +829,23 @@ static int mlm_step(rs_trainer* t, const TypeStep& ty, const int32_t* d_ids, con
         TRY_HIP(hipStreamSynchronize(st));
         return RS_OK;
     }
+    t->have_grad = false;
     TRY_HIP(hipMemsetAsync(Gm, 0, t->n_params * 4, st));
     float* dT = c.dB;
     float* dT2 = c.dF;
-    TRY_HIP(tr_colsum(c.logits, nullptr, nullptr, R, V, 0, c.part, Gm + t->o_db, 0, st));
-    RS_TRY(gemm_tn(t, st, R, V, H, c.logits, c.th, Gm + t->o_word, 0.f));          // tied decoder part
+    // a frozen tensor's gradient is not launched (the tied decoder's part of the word embeddings with them)
+    if (t->on(t->o_db)) TRY_HIP(tr_colsum(c.logits, nullptr, nullptr, R, V, 0, c.part, Gm + t->o_db, 0, st));
+    if (t->on(t->o_word)) RS_TRY(gemm_tn(t, st, R, V, H, c.logits, c.th, Gm + t->o_word, 0.f));   // tied decoder part
     RS_TRY(gemm_nn(t, st, R, V, H, c.logits, Pm + t->o_word, dT, 0.f));
-    TRY_HIP(tr_colsum_ln(dT, c.tx, c.tst, R, H, c.part, Gm + t->o_tg, Gm + t->o_tb, st));
+    if (t->on(t->o_tg) || t->on(t->o_tb))
+        TRY_HIP(tr_colsum_ln(dT, c.tx, c.tst, R, H, c.part, Gm + t->o_tg, Gm + t->o_tb, st));
     TRY_HIP(tr_ln_bwd(dT, c.tx, c.tst, Pm + t->o_tg, dT2, R, H, st));
     TRY_HIP(tr_gelu_bwd(dT2, c.tpre, (long long)R * H, st));
-    TRY_HIP(tr_colsum(dT2, nullptr, nullptr, R, H, 0, c.part, Gm + t->o_bt, 0, st));
-    RS_TRY(gemm_tn(t, st, R, H, H, dT2, hfin, Gm + t->o_wt, 0.f));
-    if (h_lab) {
+    if (t->on(t->o_bt)) TRY_HIP(tr_colsum(dT2, nullptr, nullptr, R, H, 0, c.part, Gm + t->o_bt, 0, st));
+    if (t->on(t->o_wt)) RS_TRY(gemm_tn(t, st, R, H, H, dT2, hfin, Gm + t->o_wt, 0.f));
+    if (!bwd_plan(t).any()) {
+        // only the head is trainable: nothing takes the gradient of the hidden state
+    } else if (h_lab) {
         // d hidden of the labelled rows into dT (free since tr_ln_bwd), then every row of dA
         RS_TRY(gemm_nn(t, st, R, H, H, dT2, Pm + t->o_wt, dT, 0.f));
         TRY_HIP(tr_expand_rows(dT, c.dm + c.i_linv, M, H, c.dA, st));
@@ -747,6 +856,7 @@ static int mlm_step(rs_trainer* t, const TypeStep& ty, const int32_t* d_ids, con
     if (int r = adamw(t, o, st)) return r;
     TRY_HIP(hipStreamSynchronize(st));
     if (tr_sgemm_failed()) return rs_fail(RS_EHIP, "a stream-K GEMM timed out waiting for a partial tile");
+    t->have_grad = true;
     return RS_OK;
 }
 
@@ -784,6 +894,156 @@ int rs_train_step_mlm_labeled(rs_trainer* t, const int32_t* d_ids, const int32_t
                                         std::to_string(h_lab_row[k - 1]) + " (strictly ascending rows)");
     }
     return mlm_step(t, ty, d_ids, h_seq_off, n_seq, h_key_len, h_lab_row, n_lab, d_lab_id, o, d_loss, stream);
+}
+
+}  // extern "C"
+
+namespace {
+
+// HF aliases of one Parameter (BertForMaskedLM ties the decoder to the word embeddings and to
+// cls.predictions.bias): the key the trainer's table holds
+std::string table_key(const rs_trainer* t, const std::string& k) {
+    if (t->cfg.heads_mask == RS_HEAD_MLM) {
+        if (k == "cls.predictions.decoder.weight") return "bert.embeddings.word_embeddings.weight";
+        if (k == "cls.predictions.decoder.bias") return "cls.predictions.bias";
+    }
+    return k;
+}
+
+// whole dotted components: the key is the prefix, or starts with prefix + "."
+bool prefix_matches(const std::string& key, const std::string& prefix) {
+    return key.compare(0, prefix.size(), prefix) == 0 && (key.size() == prefix.size() || key[prefix.size()] == '.');
+}
+
+int clear_accum(rs_trainer* t, hipStream_t st) {
+    if (t->A.p) TRY_HIP(hipMemsetAsync(t->A.p, 0, t->n_params * 4, st));
+    t->acc_filled = false;
+    return RS_OK;
+}
+
+// the gradient source of rs_trainer_apply / rs_trainer_grad_norm
+int grad_source(rs_trainer* t, int32_t source, const float** src) {
+    if (source != 0 && source != 1)
+        return rs_fail(RS_EARG, "source must be 0 (the last step's gradient) or 1 (the accumulator)");
+    if (source == 0 && !t->have_grad)
+        return rs_fail(RS_ESTATE, "no gradient: no backward has run (since the trainable set last changed)");
+    if (source == 1 && !t->acc_filled) return rs_fail(RS_ESTATE, "the accumulator is empty");
+    if (t->ranges.empty()) return rs_fail(RS_ESTATE, "every tensor is frozen");
+    *src = source == 0 ? t->G.as<float>() : t->A.as<float>();
+    return RS_OK;
+}
+
+// sqrt of the ordered float64 sum of squares over the trainable ranges; synchronises the stream
+int grad_norm(rs_trainer* t, const float* src, double* norm, hipStream_t st) {
+    TRY_ALLOC(t->nws.ensure(tr_sumsq_ws_doubles((int)t->ranges.size()) * 8));
+    TRY_HIP(tr_sumsq(src, t->ranges.data(), (int)t->ranges.size(), t->nws.as<double>(), st));
+    double ss = 0.0;
+    TRY_HIP(hipMemcpyAsync(&ss, t->nws.p, 8, hipMemcpyDeviceToHost, st));
+    TRY_HIP(hipStreamSynchronize(st));
+    *norm = std::sqrt(ss);
+    return RS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rs_trainer_set_trainable(rs_trainer* t, const char* hf_key_prefix, int32_t trainable) {
+    if (!t || !hf_key_prefix) return rs_fail(RS_EARG, "null argument");
+    if (t->acc_filled)
+        return rs_fail(RS_ESTATE, "the accumulator holds gradients: apply or clear it before changing what is trainable");
+    std::string pre(hf_key_prefix);
+    while (!pre.empty() && pre.back() == '.') pre.pop_back();
+    if (pre.empty()) return rs_fail(RS_EARG, "empty prefix");
+    std::vector<std::string> keys;
+    for (auto& kv : t->table) keys.push_back(kv.first);
+    if (t->cfg.heads_mask == RS_HEAD_MLM) {
+        keys.push_back("cls.predictions.decoder.weight");
+        keys.push_back("cls.predictions.decoder.bias");
+    }
+    int n = 0;
+    for (const std::string& k : keys) {
+        if (!prefix_matches(k, pre)) continue;
+        const size_t off = t->table[table_key(t, k)].first;
+        if (trainable) t->frozen.erase(off);
+        else t->frozen.insert(off);
+        ++n;
+    }
+    if (!n) return rs_fail(RS_EARG, "no tensor matches the prefix " + pre);
+    merge_ranges(t);
+    t->have_grad = false;      // t->G was computed for another trainable set
+    return RS_OK;
+}
+
+int rs_trainer_is_trainable(const rs_trainer* t, const char* hf_key) {
+    if (!t || !hf_key) return rs_fail(RS_EARG, "null argument");
+    auto it = t->table.find(table_key(t, hf_key));
+    if (it == t->table.end()) return rs_fail(RS_EARG, std::string("unknown tensor ") + hf_key);
+    return t->on(it->second.first) ? 1 : 0;
+}
+
+int rs_trainer_accumulate(rs_trainer* t, float weight, void* stream) {
+    if (!t) return rs_fail(RS_EARG, "null trainer");
+    if (!t->finalized) return rs_fail(RS_ESTATE, "rs_trainer_finalize not called");
+    if (!t->have_grad)
+        return rs_fail(RS_ESTATE, "no gradient to accumulate: no backward has run (since the trainable set last changed)");
+    hipStream_t st = (hipStream_t)stream;
+    TRY_HIP(hipSetDevice(t->device));
+    if (!t->A.p) {
+        TRY_ALLOC(t->A.ensure(t->n_params * 4));
+        TRY_HIP(hipMemsetAsync(t->A.p, 0, t->n_params * 4, st));
+    }
+    for (const TrRange& r : t->ranges)
+        TRY_HIP(tr_accum(t->A.as<float>() + r.off, t->G.as<float>() + r.off, r.n, weight, st));
+    t->acc_filled = true;
+    return RS_OK;
+}
+
+int rs_trainer_zero_accum(rs_trainer* t) {
+    if (!t) return rs_fail(RS_EARG, "null trainer");
+    TRY_HIP(hipSetDevice(t->device));
+    TRY_HIP(hipDeviceSynchronize());
+    if (t->A.p) TRY_HIP(hipMemset(t->A.p, 0, t->n_params * 4));
+    t->acc_filled = false;
+    return RS_OK;
+}
+
+int rs_trainer_grad_norm(rs_trainer* t, int32_t source, double* h_norm, void* stream) {
+    if (!t || !h_norm) return rs_fail(RS_EARG, "null argument");
+    if (!t->finalized) return rs_fail(RS_ESTATE, "rs_trainer_finalize not called");
+    const float* src = nullptr;
+    if (int r = grad_source(t, source, &src)) return r;
+    TRY_HIP(hipSetDevice(t->device));
+    return grad_norm(t, src, h_norm, (hipStream_t)stream);
+}
+
+int rs_trainer_apply(rs_trainer* t, const rs_train_opts* o, const rs_apply_opts* a, double* h_norm,
+                     int32_t* h_applied, void* stream) {
+    if (!t || !o || !a) return rs_fail(RS_EARG, "null argument");
+    if (!t->finalized) return rs_fail(RS_ESTATE, "rs_trainer_finalize not called");
+    if (!std::isfinite(a->grad_scale)) return rs_fail(RS_EARG, "grad_scale must be finite");
+    const float* src = nullptr;
+    if (int r = grad_source(t, a->source, &src)) return r;
+    hipStream_t st = (hipStream_t)stream;
+    TRY_HIP(hipSetDevice(t->device));
+    double n = 0.0;
+    if (int r = grad_norm(t, src, &n, st)) return r;
+    n *= std::fabs((double)a->grad_scale);
+    if (h_norm) *h_norm = n;
+    if (h_applied) *h_applied = 0;
+    if (!std::isfinite(n)) {                   // the skipped step of a non-finite gradient: nothing moves
+        if (a->source == 1) RS_TRY(clear_accum(t, st));
+        TRY_HIP(hipStreamSynchronize(st));
+        return RS_OK;
+    }
+    // clip_grad_norm_'s coefficient; the gradient's whole multiplier rounded once
+    const double c = a->max_grad_norm > 0.f ? std::min(1.0, (double)a->max_grad_norm / (n + 1e-6)) : 1.0;
+    const float gmul = (float)((double)a->grad_scale * c);
+    RS_TRY(adamw_ranges(t, o, src, gmul, st));
+    if (a->source == 1) RS_TRY(clear_accum(t, st));
+    TRY_HIP(hipStreamSynchronize(st));
+    if (h_applied) *h_applied = 1;
+    return RS_OK;
 }
 
 int rs_trainer_reset_optimizer(rs_trainer* t) {
@@ -831,7 +1091,8 @@ void rs_trainer_destroy(rs_trainer* t) {
     (void)hipSetDevice(t->device);
     (void)hipDeviceSynchronize();
     if (t->blas) (void)rocblas_destroy_handle(t->blas);
-    for (DevBuf* b : {&t->P, &t->G, &t->M1, &t->V1, &t->act, &t->grad, &t->meta, &t->small, &t->ws}) b->release();
+    for (DevBuf* b : {&t->P, &t->G, &t->M1, &t->V1, &t->act, &t->grad, &t->meta, &t->small, &t->ws, &t->A, &t->nws})
+        b->release();
     delete t;
 }
 

@@ -73,6 +73,32 @@ def param_shapes(shape: BertShape, head: str = "cls") -> Dict[str, Tuple[int, ..
     return out
 
 
+def prefix_matches(key: str, prefix: str) -> bool:
+    """The rule ``freeze`` / ``unfreeze`` select tensors by (``rs_trainer_set_trainable``): whole dotted
+    components, i.e. ``key`` equals ``prefix`` or starts with ``prefix + "."``; a trailing ``.`` of the
+    prefix is ignored and an empty prefix matches nothing.  ``bert.encoder.layer.1`` selects layer 1 and
+    not layer 10; the child names the reference's ``util/freezer.py`` takes (``bert``, ``linear``,
+    ``cls``) work as they are."""
+    prefix = prefix.rstrip(".")
+    return bool(prefix) and (key == prefix or key.startswith(prefix + "."))
+
+
+def lr_at(step: int, total_steps: int, warmup_steps: int, base_lr: float, schedule: str = "constant") -> float:
+    """Learning rate of 0-based optimizer step ``step`` of a run of ``total_steps``: ``constant``, or
+    ``linear``, the multiplier of transformers' ``get_linear_schedule_with_warmup`` (``step /
+    max(1, warmup)`` below the warm-up, ``max(0, (total - step) / max(1, total - warmup))`` after)."""
+    if schedule == "constant":
+        return float(base_lr)
+    if schedule != "linear":
+        raise ValueError(f"unknown lr schedule {schedule!r} (constant, linear)")
+    if step < warmup_steps:
+        return float(base_lr) * (step / max(1, warmup_steps))
+    return float(base_lr) * max(0.0, (total_steps - step) / max(1, total_steps - warmup_steps))
+
+
+_SOURCES = {"last": 0, "accum": 1}
+
+
 class _Trainer:
     HEAD = "cls"
 
@@ -162,8 +188,65 @@ class _Trainer:
     def tensor(self, key: str) -> np.ndarray:
         return self._get(self.lib.rs_trainer_get_tensor, key)
 
-    def grad(self, key: str) -> np.ndarray:
+    def grad(self, key: str) -> Optional[np.ndarray]:
+        """The last step's gradient of a tensor; ``None`` for a frozen one (torch's ``.grad``)."""
+        if not self.is_trainable(key):
+            return None
         return self._get(self.lib.rs_trainer_get_grad, key)
+
+    def accum(self, key: str) -> Optional[np.ndarray]:
+        """The accumulated (weighted sum of micro-batch) gradient of a tensor; ``None`` if frozen."""
+        if not self.is_trainable(key):
+            return None
+        return self._get(self.lib.rs_trainer_get_accum, key)
+
+    def _set_trainable(self, prefixes, flag: int) -> None:
+        for p in prefixes:
+            _lib.check(self.lib.rs_trainer_set_trainable(self.handle, str(p).encode(), flag))
+
+    def freeze(self, *prefixes: str) -> None:
+        """``requires_grad = False`` on every tensor a prefix selects (``prefix_matches``; the
+        reference's ``util/freezer.py`` ``freeze_by_name``): no AdamW update or decay, no part in the
+        gradient norm or the accumulation, and its gradient kernels are not launched.  On an MLM
+        trainer ``cls`` holds the tied decoder, so it freezes the word embeddings too."""
+        self._set_trainable(prefixes, 0)
+
+    def unfreeze(self, *prefixes: str) -> None:
+        self._set_trainable(prefixes, 1)
+
+    def is_trainable(self, key: str) -> bool:
+        rc = self.lib.rs_trainer_is_trainable(self.handle, key.encode())
+        if rc < 0:
+            _lib.check(rc)
+        return bool(rc)
+
+    def accumulate(self, weight: float = 1.0) -> None:
+        """Adds ``weight`` times the last step's gradient (a ``step(update=False)``) to the accumulator."""
+        _lib.check(self.lib.rs_trainer_accumulate(self.handle, float(weight), _lib.stream_ptr(self.device)))
+
+    def zero_accum(self) -> None:
+        _lib.check(self.lib.rs_trainer_zero_accum(self.handle))
+
+    def grad_norm(self, source: str = "accum") -> float:
+        """float64 L2 norm over the trainable tensors of the accumulator or the last gradient."""
+        n = ctypes.c_double()
+        _lib.check(self.lib.rs_trainer_grad_norm(self.handle, _SOURCES[source], ctypes.byref(n),
+                                                 _lib.stream_ptr(self.device)))
+        return n.value
+
+    def apply(self, grad_scale: float = 1.0, max_grad_norm: Optional[float] = None, source: str = "accum",
+              lr: Optional[float] = None) -> Tuple[float, bool]:
+        """One AdamW step on ``grad_scale`` times the accumulator (or the last gradient), clipped to
+        ``max_grad_norm`` like ``clip_grad_norm_``; ``lr`` overrides the trainer's for this step.
+        Returns (the norm before clipping, whether the step was taken: a non-finite norm skips it)."""
+        a = _lib.RsApplyOpts(_SOURCES[source], float(grad_scale), float(max_grad_norm or 0.0))
+        o = _lib.RsTrainOpts.from_buffer_copy(self.opts)
+        if lr is not None:
+            o.lr = float(lr)
+        n, ok = ctypes.c_double(), ctypes.c_int32()
+        _lib.check(self.lib.rs_trainer_apply(self.handle, ctypes.byref(o), ctypes.byref(a), ctypes.byref(n),
+                                             ctypes.byref(ok), _lib.stream_ptr(self.device)))
+        return n.value, bool(ok.value)
 
     def state_dict(self) -> Dict[str, np.ndarray]:
         """HF-keyed weights (what the scorers load); the pooler passes through unchanged, the
@@ -309,8 +392,38 @@ class MLMTrainer(_Trainer):
         return float(loss.item())
 
 
+class _Grouped:
+    """The optimizer side of an epoch helper.  With the defaults (``accum_steps`` 1, no clipping, no
+    schedule) a batch is one ``tr.step(update=update)``, as it always was.  Otherwise (training
+    passes only) every batch runs ``step(update=False)`` + ``accumulate(w)`` and each group of
+    ``accum_steps`` consecutive batches (the last may be shorter) ends in one ``apply`` with
+    ``grad_scale`` = 1 (``mean`` False: summed losses) or 1 / sum of the weights (``mean`` True), at
+    the lr ``lr_of_step`` gives for the run's 0-based optimizer step."""
+
+    def __init__(self, tr: _Trainer, update, accum_steps: int, max_grad_norm, lr_of_step, mean: bool):
+        if accum_steps < 1:
+            raise ValueError("accum_steps must be at least 1")
+        self.tr, self.k, self.clip, self.lr_of, self.mean = tr, int(accum_steps), max_grad_norm, lr_of_step, mean
+        self.plain = update is not True or (self.k == 1 and max_grad_norm is None and lr_of_step is None)
+        self.update = update if self.plain else False
+        self.n, self.wsum, self.opt_step = 0, 0.0, 0
+
+    def after_step(self, weight: float, last: bool) -> None:
+        if self.plain:
+            return
+        self.tr.accumulate(weight)
+        self.n += 1
+        self.wsum += weight
+        if self.n == self.k or last:
+            self.tr.apply(grad_scale=1.0 / self.wsum if self.mean else 1.0, max_grad_norm=self.clip,
+                          lr=None if self.lr_of is None else self.lr_of(self.opt_step))
+            self.n, self.wsum = 0, 0.0
+            self.opt_step += 1
+
+
 def rescorebert_epoch(tr: RescoreBertTrainer, tokens, hyp_off, target, am, cer, batch_size: int, n_best: int,
-                      update=True, token_types=None) -> float:
+                      update=True, token_types=None, accum_steps: int = 1, max_grad_norm: Optional[float] = None,
+                      lr_of_step=None) -> float:
     """One pass of RescoreBert/main.py:82-163 run_one_epoch(train=True) over the hypotheses in
     order: batches of ``batch_size * n_best`` rows (set_dataloader :71-79, shuffle False),
     groups of ``n_best`` (``reference_groups``) for MD_MWER / MD_MWED, which reshape the batch
@@ -318,11 +431,15 @@ def rescorebert_epoch(tr: RescoreBertTrainer, tokens, hyp_off, target, am, cer, 
     (:104-110) and takes any batch, ragged last batch and short N-best lists included;
     ``update`` True = grad_update (the caller resets AdamW first, as the reference builds it per
     call), "loss" = the dev pass.  ``token_types``: per-token segment ids, sliced with the tokens.
+    ``accum_steps`` / ``max_grad_norm`` / ``lr_of_step`` (``_Grouped``): the losses are sums over
+    utterances, so k accumulated micro-batches (weight 1, scale 1) are the one batch holding all of them.
     Returns the epoch loss (mean of the batch losses)."""
     hoff = np.asarray(hyp_off, np.int64)
     n = len(hoff) - 1
     rows = batch_size * n_best
     tot, nb = 0.0, 0
+    grp = _Grouped(tr, update, accum_steps, max_grad_norm, lr_of_step, mean=False)
+    update = grp.update
     for b0 in range(0, n, rows):
         b1 = min(n, b0 + rows)
         t0, t1 = int(hoff[b0]), int(hoff[b1])
@@ -330,21 +447,27 @@ def rescorebert_epoch(tr: RescoreBertTrainer, tokens, hyp_off, target, am, cer, 
         loss, _ = tr.step(np.asarray(tokens[t0:t1]), (hoff[b0:b1 + 1] - t0).astype(np.int32),
                           groups, target[b0:b1], am[b0:b1], cer[b0:b1], update=update,
                           token_types=None if token_types is None else np.asarray(token_types[t0:t1]))
+        grp.after_step(1.0, b1 == n)
         tot += loss
         nb += 1
     return tot / max(nb, 1)
 
 
 def mlm_epoch(tr: MLMTrainer, seqs: Sequence[Sequence[int]], labels: Sequence[Sequence[int]], batch_size: int,
-              update=True, order=None, token_types=None, ignore_index: Optional[int] = None) -> float:
+              update=True, order=None, token_types=None, ignore_index: Optional[int] = None, accum_steps: int = 1,
+              max_grad_norm: Optional[float] = None, lr_of_step=None) -> float:
     """One pass of MLM_PLL/main.py:73-114 run_one_epoch (do_scoring False) over do_job rows:
     batches of ``batch_size`` rows (in ``order``, default as given), padded as the reference's
     collate pads them (``pad_rows``).  ``token_types``: a segment-id row per sequence, padded with
     the ids.  ``ignore_index``: labels equal to it carry no loss (``MLMTrainer.step``); the labels are
-    then padded with it, so every batch needs a labelled position.  Returns the epoch loss (mean of
-    the batch losses)."""
+    then padded with it, so every batch needs a labelled position.  ``accum_steps`` / ``max_grad_norm``
+    / ``lr_of_step`` (``_Grouped``): a batch is weighted by its number of loss positions and the group
+    scaled by 1 / their sum, the CE mean over the group.  Returns the epoch loss (mean of the batch
+    losses)."""
     idx = np.arange(len(seqs)) if order is None else np.asarray(order)
     tot, nb = 0.0, 0
+    grp = _Grouped(tr, update, accum_steps, max_grad_norm, lr_of_step, mean=True)
+    update = grp.update
     for b0 in range(0, len(idx), batch_size):
         sel = idx[b0:b0 + batch_size]
         tt = None if token_types is None else [token_types[i] for i in sel]
@@ -352,6 +475,8 @@ def mlm_epoch(tr: MLMTrainer, seqs: Sequence[Sequence[int]], labels: Sequence[Se
                                              label_pad=0 if ignore_index is None else ignore_index)
         tot += tr.step(ids, off, lab, klen, update=update, token_types=typ[0] if typ else None,
                        ignore_index=ignore_index)
+        grp.after_step(float(len(lab) if ignore_index is None else np.count_nonzero(lab != ignore_index)),
+                       b0 + batch_size >= len(idx))
         nb += 1
     return tot / max(nb, 1)
 
@@ -413,19 +538,24 @@ def mask_tokens(seqs: Sequence[Sequence[int]], shape: BertShape, seed, mlm_proba
 
 
 def mlm_epoch_dynamic(tr: MLMTrainer, sentences: Sequence[Sequence[int]], batch_size: int, seed: Sequence[int],
-                      update=True, order=None, mlm_probability: float = 0.15, continuation=None) -> float:
+                      update=True, order=None, mlm_probability: float = 0.15, continuation=None, accum_steps: int = 1,
+                      max_grad_norm: Optional[float] = None, lr_of_step=None) -> float:
     """One pass over ``[CLS] w.. [SEP]`` rows (one per sentence) with dynamic masking: batch b (of
     ``batch_size`` rows, in ``order``) is masked by ``mask_tokens`` seeded ``(*seed, b)``, so every
     batch has a labelled position and a pass is a function of ``seed`` alone; labelled steps
-    (``ignore_index`` -100).  Returns the epoch loss (mean of the batch losses)."""
+    (``ignore_index`` -100); ``accum_steps`` / ``max_grad_norm`` / ``lr_of_step`` as ``mlm_epoch``.
+    Returns the epoch loss (mean of the batch losses)."""
     idx = np.arange(len(sentences)) if order is None else np.asarray(order)
     tot, nb = 0.0, 0
+    grp = _Grouped(tr, update, accum_steps, max_grad_norm, lr_of_step, mean=True)
+    update = grp.update
     for b0 in range(0, len(idx), batch_size):
         sel = idx[b0:b0 + batch_size]
         rows, labs = mask_tokens([sentences[i] for i in sel], tr.shape, tuple(seed) + (nb,), mlm_probability,
                                  None if continuation is None else [continuation[i] for i in sel])
         ids, off, lab, klen = pad_rows(rows, labs, label_pad=-100)
         tot += tr.step(ids, off, lab, klen, update=update, ignore_index=-100)
+        grp.after_step(float(np.count_nonzero(lab != -100)), b0 + batch_size >= len(idx))
         nb += 1
     return tot / max(nb, 1)
 

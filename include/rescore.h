@@ -460,6 +460,54 @@ int rs_dropout_keep(uint32_t seed, uint64_t step, uint32_t site, float p, int64_
 /* Synchronous copies of one parameter / its last gradient (numel must match). */
 int rs_trainer_get_tensor(rs_trainer* t, const char* hf_key, void* host_out, int64_t numel);
 int rs_trainer_get_grad(rs_trainer* t, const char* hf_key, void* host_out, int64_t numel);
+/* ---- Gradient accumulation, clipping and frozen tensors ------------------------------------
+ * None of these changes a step that does not use them: with no entry below called, every
+ * rs_train_step_* is what it was, bit for bit (kernels, launches, dropout keys).
+ *
+ * Frozen tensors: torch's requires_grad = False (the reference's util/freezer.py).  Every tensor
+ * whose key equals hf_key_prefix or starts with hf_key_prefix + "." (whole dotted components: a
+ * trailing '.' is ignored, "bert.encoder.layer.1" does not match layer 10) becomes trainable (1) or
+ * frozen (0); on an MLM trainer cls.predictions.decoder.weight / .bias are the word embeddings /
+ * cls.predictions.bias (one Parameter in HF), so freezing "cls" freezes the word embeddings.  A
+ * prefix that matches nothing is RS_EARG; a call while the accumulator is non-empty RS_ESTATE.
+ * Callable before or after rs_trainer_finalize; it takes effect at the next step, and the last
+ * step's gradient is dropped (accumulate / apply / grad_norm on it are RS_ESTATE until a step has
+ * run).  AdamW never touches a frozen tensor (no decay, moments kept), the gradient norm and the
+ * accumulation leave it out, rs_trainer_get_grad / _get_accum on it fail with RS_ESTATE, and the
+ * backward launches none of its gradient kernels: layers below the lowest one with a trainable
+ * tensor run no backward at all unless an embedding tensor is trainable.  Gradients and updates of
+ * the trainable tensors are bitwise those of the all-trainable step.  A step with update >= 0 while
+ * every tensor is frozen is RS_ESTATE, raised before any state (dropout counter included) moves. */
+int rs_trainer_set_trainable(rs_trainer* t, const char* hf_key_prefix, int32_t trainable);
+int rs_trainer_is_trainable(const rs_trainer* t, const char* hf_key);   /* 1 / 0 / negative error */
+/* acc = fmaf(weight, g, acc) over the trainable tensors, g the gradient of the last step (run with
+ * update = 0), enqueued on `stream`.  The accumulator is one more flat fp32 buffer (4 bytes per
+ * parameter), allocated and zeroed at the first call (RS_ENOMEM if it does not fit).  Micro-batches
+ * add in the order of the calls: bitwise reproducible.  RS_ESTATE before any backward. */
+int rs_trainer_accumulate(rs_trainer* t, float weight, void* stream);
+int rs_trainer_zero_accum(rs_trainer* t);
+/* Synchronous copy of one tensor of the accumulator (RS_ESTATE while it is empty). */
+int rs_trainer_get_accum(rs_trainer* t, const char* hf_key, void* host_out, int64_t numel);
+typedef struct rs_apply_opts {
+    int32_t source;        /* 0: the last step's gradient; 1: the accumulator */
+    float grad_scale;      /* the gradient is grad_scale * source (1/k, 1/sum n_i, ...) */
+    float max_grad_norm;   /* <= 0: no clipping */
+} rs_apply_opts;
+/* One AdamW step (opts: lr, betas, eps, weight_decay; opts->update is not read) on the gradient
+ * grad_scale * source, clipped like torch's clip_grad_norm_: n = the float64 norm of that gradient
+ * over the trainable tensors, c = min(1, max_grad_norm / (n + 1e-6)), and the update uses
+ * (float)(grad_scale * c) * source, the product rounded to fp32 once per element.  *h_norm = n (before
+ * clipping), *h_applied = 1; both nullable.  A non-finite n skips the step: no parameter, moment
+ * or step count moves, *h_applied = 0, RS_OK.  source = 1 clears the accumulator either way.
+ * After a step with update = 0, {source 0, grad_scale 1, max_grad_norm 0} leaves parameters, moments
+ * and step count exactly as that step with update = 1 would have.  RS_ESTATE for source 0 before
+ * any backward and for source 1 on an empty accumulator.  Synchronises `stream`. */
+int rs_trainer_apply(rs_trainer* t, const rs_train_opts* opts, const rs_apply_opts* a, double* h_norm,
+                     int32_t* h_applied, void* stream);
+/* *h_norm = sqrt(sum g^2) over the trainable tensors of the source, in float64: each fp32 square is
+ * exact, and the sum is a fixed two-stage ordered reduction without atomics (the same buffer gives
+ * the same bits on every run and every device).  Synchronises `stream`. */
+int rs_trainer_grad_norm(rs_trainer* t, int32_t source, double* h_norm, void* stream);
 /* A fresh AdamW state (moments and step count zeroed; MLM_PLL/main.py:76 builds its
  * optimizer inside every epoch). */
 int rs_trainer_reset_optimizer(rs_trainer* t);
