@@ -194,6 +194,24 @@ _DEBUG_SIGS = {
     "rs_debug_bertscore_recall": (CI, [P, CI, CI, P, P, CI, P, P, P]),
     # (x32, stats, g, b, himg, len, row, tok_off, s0, s1, row0, H, two, d_out, stream)
     "rs_debug_embed_out": (CI, [P, P, P, P, P, P, P, P, CI, CI, CI, CI, CI, P, P]),
+    # The layer-0 front end, dedup / multi-query attention, gathers and small heads
+    # (tests/test_gpu_front_ops.py, tests/test_gpu_attn_plan.py); meta = DebugMeta*
+    # (tok_off, len, mask, mask_end, n_seq, s0, s1, urow_h, urow_m): host int32 arrays -> urows
+    "rs_debug_plan_unique": (CI, [P, P, P, P, CI, CI, CI, P, P]),
+    # (form, tok, type, meta, s0, s1, row0, urows, mask_id, vocab, type_vocab, word, pos, typetab, g, b, eps, H,
+    #  x32, stats, h16, kx, stream): form 0 embed_ln, 1 embed_ln_set, 2 embed_unique
+    "rs_debug_embed": (CI, [CI, P, P, P, CI, CI, CI, CI, CI, CI, CI, P, P, P, P, P, ctypes.c_float, CI, P, P, P, CI, P]),
+    # (qkv, qkv32, meta, s0, s1, row0, max_len, H, heads, kx, dedup, ctx, stream)
+    "rs_debug_attention_plan": (CI, [P, CI, P, CI, CI, CI, CI, CI, CI, CI, CI, P, P]),
+    # (qkv, qkv32, meta, s0, s1, H, heads, kx, qd, x32, stats, g, b, himg, ctxq, resq, stream)
+    "rs_debug_attention_mquery": (CI, [P, CI, P, CI, CI, CI, CI, CI, P, P, P, P, P, P, P, P, P]),
+    # (op, src, ld, tok, meta, a0, a1, row0, dst, lab, llog, stream): 0 / 1 query rows per sequence / per query,
+    # 2 / 3 labels per sequence / per query; (a0, a1) = (s0, s1) or (q0, n)
+    "rs_debug_gather": (CI, [CI, P, CI, P, P, CI, CI, CI, P, P, P, P]),
+    # (h, rows, H, w, b, out, stream)
+    "rs_debug_cls_linear": (CI, [P, CI, CI, P, P, P, P]),
+    # (row_lp, off, n, out, stream)
+    "rs_debug_segsum": (CI, [P, P, CI, P, P]),
 }
 
 
@@ -201,6 +219,13 @@ class DebugGemmEpi(ctypes.Structure):
     """The EpiArgs fields rs_debug_gemm_epi takes (csrc/k_gemm.hip DebugGemmEpi)."""
     _fields_ = [(n, P) for n in ("bias", "res", "res_stats", "res_g", "res_b", "out", "res_o16", "res_stats0",
                                  "res_g0", "res_b0")] + [(n, CI) for n in ("ldc", "m_valid", "kx", "nlog")]
+
+
+class DebugMeta(ctypes.Structure):
+    """Device int32 metadata arrays of the front-end / attention test entries (csrc/common.h DebugMeta):
+    SeqMeta's columns, then QueryMeta's (qlabel = its label).  Unused ones stay null."""
+    _fields_ = [(n, P) for n in ("tok_off", "len", "mask_pos", "mask_end", "query", "label", "row", "urow_h", "urow_m",
+                                 "first", "seq", "pos", "qlabel")]
 
 
 

@@ -158,6 +158,21 @@ struct QueryMeta {
     const int* label;      // [n_q] label id, -1 = take tokens[tok_off + pos]
 };
 
+// The metadata the test entries rs_debug_embed / _attention_plan / _attention_mquery / _gather take
+// (tests only; mirrored as _lib.DebugMeta): device int32 arrays, SeqMeta's then QueryMeta's (qlabel =
+// QueryMeta.label).  An entry checks the ones its kernels read and leaves the others null.
+struct DebugMeta {
+    const int *tok_off, *len, *mask_pos, *mask_end, *query, *label, *row, *urow_h, *urow_m;
+    const int *first, *seq, *pos, *qlabel;
+};
+inline SeqMeta debug_seq_meta(const DebugMeta& d) {
+    SeqMeta sm{};
+    sm.tok_off = d.tok_off; sm.len = d.len; sm.mask_pos = d.mask_pos; sm.query = d.query; sm.label = d.label;
+    sm.row = d.row; sm.urow_h = d.urow_h; sm.urow_m = d.urow_m; sm.mask_end = d.mask_end;
+    return sm;
+}
+inline QueryMeta debug_query_meta(const DebugMeta& d) { return QueryMeta{d.first, d.seq, d.pos, d.qlabel}; }
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);

@@ -906,3 +906,35 @@ extern "C" int rs_debug_attention_query(const void* qkv, int qkv32, const int* l
                                                 (f16*)ctxq, resq, kx, (hipStream_t)stream, qd, (const f16*)himg);
     return e == hipSuccess ? 0 : -2;
 }
+
+// Test entry (not part of the scoring path): launch_attention_full with every argument given, over
+// sequences [s0, s1) of the DebugMeta arrays — dedup != 0: qkv holds the chunk's unique rows (SeqRows:
+// urow_h, urow_m, mask_pos, mask_end), else rows row[s] - row0 + t.  ctx: the kx image at rows
+// row[s] - row0 + t in both forms.  The launcher's own rejections (dedup with another kx than the
+// type's, fp32 dedup past 64 keys) come back as -2.
+extern "C" int rs_debug_attention_plan(const void* qkv, int qkv32, const DebugMeta* dm, int s0, int s1, int row0,
+                                       int max_len, int H, int heads, int kx, int dedup, void* ctx, void* stream) {
+    if (!qkv || !dm || !ctx || !dm->len || !dm->row) return -1;
+    if (s0 < 0 || s1 <= s0 || max_len <= 0 || heads <= 0 || H != heads * 64 || kx < 1 || kx > 3) return -1;
+    if (dedup && (!dm->urow_h || !dm->urow_m || !dm->mask_pos || !dm->mask_end)) return -1;
+    const hipError_t e = launch_attention_full(qkv, qkv32 != 0, debug_seq_meta(*dm), s0, s1, row0, H, heads, (f16*)ctx,
+                                               kx, (hipStream_t)stream, dedup != 0, max_len);
+    return e == hipSuccess ? 0 : -2;
+}
+
+// Test entry (not part of the scoring path): launch_attention_mquery over every query of sequences
+// [s0, s1) (DebugMeta: len, row, first, pos).  Arguments as rs_debug_attention_query; qd null or the
+// dense Q [queries, H], ctxq / resq row q - first[s0].
+extern "C" int rs_debug_attention_mquery(const void* qkv, int qkv32, const DebugMeta* dm, int s0, int s1, int H,
+                                         int heads, int kx, const void* qd, const float* x32, const void* stats,
+                                         const float* g, const float* b, const void* himg, void* ctxq, float* resq,
+                                         void* stream) {
+    if (!qkv || !dm || !ctxq || !resq || !dm->len || !dm->row || !dm->first || !dm->pos) return -1;
+    if (s0 < 0 || s1 <= s0 || heads <= 0 || H != heads * 64) return -1;
+    if (kx != 1 && kx != 3) return -1;
+    if (!himg && (!x32 || !stats || !g || !b)) return -1;
+    const hipError_t e = launch_attention_mquery(qkv, qkv32 != 0, x32, (const float2*)stats, g, b, debug_seq_meta(*dm),
+                                                 debug_query_meta(*dm), s0, s1, H, heads, (f16*)ctxq, resq, kx,
+                                                 (hipStream_t)stream, qd, (const f16*)himg);
+    return e == hipSuccess ? 0 : -2;
+}

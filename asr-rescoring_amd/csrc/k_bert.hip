@@ -742,3 +742,80 @@ extern "C" int rs_debug_embed_out(const float* x32, const void* stats, const flo
                                           (hipStream_t)stream, (const f16*)himg, two != 0);
     return e == hipSuccess ? 0 : -2;
 }
+
+// Test entries (not part of the scoring path) for tests/test_gpu_front_ops.py: the layer-0 front end,
+// the scored-row gathers and the two small heads, each through its production launcher.  The metadata
+// is a DebugMeta of device int32 arrays (common.h); every entry returns -1 without launching on a
+// bad argument and -2 when the launcher reports an error.
+
+// form 0 launch_embed_ln (rows row[s] - row0 + t), 1 launch_embed_ln_set ([MASK] at the positions
+// pos[first[s] .. first[s + 1]); rows row[s] + t, row0 must be 0), 2 launch_embed_unique (h16 = the
+// unique-row image [>= urows, kx H]; x32 / stats unused, row0 must be 0).  tok (and type, nullable) are
+// indexed by tok_off[s] + t; word [vocab, H], pos [>= longest T, H], typetab [type_vocab, H], g, b [H].
+// Forms 0 / 1: any of x32 [rows, H], stats [rows, 2], h16 [rows, kx H] may be null, not all three.
+extern "C" int rs_debug_embed(int form, const int* tok, const int* type, const DebugMeta* dm, int s0, int s1, int row0,
+                              int urows, int mask_id, int vocab, int type_vocab, const float* word, const float* pos,
+                              const float* typetab, const float* g, const float* b, float eps, int H, float* x32,
+                              void* stats, void* h16, int kx, void* stream) {
+    if (!tok || !dm || !word || !pos || !typetab || !g || !b) return -1;
+    if (form < 0 || form > 2 || s0 < 0 || s1 <= s0 || vocab <= 0 || type_vocab <= 0) return -1;
+    if (H <= 0 || H % 256 || H > 1024 || kx < 1 || kx > 3) return -1;
+    if (!dm->tok_off || !dm->len) return -1;
+    const SeqMeta sm = debug_seq_meta(*dm);
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e;
+    if (form == 2) {
+        if (!dm->mask_pos || !dm->urow_h || !dm->urow_m || !h16 || urows <= 0 || row0 != 0) return -1;
+        e = launch_embed_unique(tok, type, sm, s0, s1, urows, mask_id, vocab, type_vocab, word, pos, typetab, g, b, eps, H,
+                                (f16*)h16, kx, st);
+    } else {
+        if (!dm->row || (!x32 && !stats && !h16)) return -1;
+        if (form == 1) {
+            if (!dm->first || !dm->pos || row0 != 0) return -1;
+            e = launch_embed_ln_set(tok, type, sm, debug_query_meta(*dm), s0, s1, mask_id, vocab, type_vocab, word, pos,
+                                    typetab, g, b, eps, H, x32, (float2*)stats, (f16*)h16, kx, st);
+        } else {
+            if (!dm->mask_pos || !dm->mask_end) return -1;
+            e = launch_embed_ln(tok, type, sm, s0, s1, row0, mask_id, vocab, type_vocab, word, pos, typetab, g, b, eps, H,
+                                x32, (float2*)stats, (f16*)h16, kx, st);
+        }
+    }
+    return e == hipSuccess ? 0 : -2;
+}
+
+// op 0 launch_gather_query_rows over sequences [a0, a1) (source row row[s] - row0 + query[s]),
+// 1 launch_gather_query_rows_list over the n = a1 queries from a0 (source row row[seq[q]] + pos[q]),
+// 2 launch_gather_labels over sequences [a0, a1), 3 launch_gather_labels_list over a1 queries from a0.
+// src / dst: fp16 rows of ld halfs (ops 0, 1); tok (nullable), lab (int) and llog (float) (ops 2, 3).
+extern "C" int rs_debug_gather(int op, const void* src, int ld, const int* tok, const DebugMeta* dm, int a0, int a1,
+                               int row0, void* dst, int* lab, float* llog, void* stream) {
+    if (!dm || op < 0 || op > 3 || a0 < 0) return -1;
+    const bool list = op == 1 || op == 3, rows = op <= 1;
+    if (list ? a1 <= 0 : a1 <= a0) return -1;
+    if (rows ? (!src || !dst || ld <= 0 || !dm->row) : (!lab || !llog)) return -1;
+    if (list ? (!dm->seq || !dm->pos || (!rows && !dm->qlabel)) : (!dm->query || (!rows && !dm->label))) return -1;
+    if (!rows && tok && !dm->tok_off) return -1;
+    if (list && row0 != 0) return -1;
+    const SeqMeta sm = debug_seq_meta(*dm);
+    const QueryMeta qm = debug_query_meta(*dm);
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e;
+    if (op == 0) e = launch_gather_query_rows((const f16*)src, ld, sm, a0, a1, row0, (f16*)dst, st);
+    else if (op == 1) e = launch_gather_query_rows_list((const f16*)src, ld, sm, qm, a0, a1, (f16*)dst, st);
+    else if (op == 2) e = launch_gather_labels(tok, sm, a0, a1, lab, llog, st);
+    else e = launch_gather_labels_list(tok, sm, qm, a0, a1, lab, llog, st);
+    return e == hipSuccess ? 0 : -2;
+}
+
+// launch_cls_linear: out[r] = h[r] . w + b[0], h [rows, H] fp32.
+extern "C" int rs_debug_cls_linear(const float* h, int rows, int H, const float* w, const float* b, float* out,
+                                   void* stream) {
+    if (!h || !w || !b || !out || rows <= 0 || H <= 0) return -1;
+    return launch_cls_linear(h, rows, H, w, b, out, (hipStream_t)stream) == hipSuccess ? 0 : -2;
+}
+
+// launch_segsum_f64: out[h] = the float64 sum of row_lp[off[h] .. off[h + 1]) in row order, off [n + 1].
+extern "C" int rs_debug_segsum(const float* row_lp, const int* off, int n, double* out, void* stream) {
+    if (!row_lp || !off || !out || n <= 0) return -1;
+    return launch_segsum_f64(row_lp, off, n, out, (hipStream_t)stream) == hipSuccess ? 0 : -2;
+}

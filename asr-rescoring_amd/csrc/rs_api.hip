@@ -1420,6 +1420,24 @@ int rs_debug_bertscore_recall(const void* d_emb, int32_t H, int32_t two, const i
     return RS_OK;
 }
 
+// Test entry (host only, no GPU call): plan_unique_rows (seq_plan.h) on the caller's host arrays
+// tok_off / len / mask / mask_end [n_seq] for the chunk [s0, s1).  Fills urow_h / urow_m [n_seq] at
+// [s0, s1) (the other entries are left as given) and returns the chunk's unique-row count (0: dedup
+// not applicable), or a negative RS_E* code.
+int rs_debug_plan_unique(const int32_t* tok_off, const int32_t* len, const int32_t* mask, const int32_t* mask_end,
+                         int32_t n_seq, int32_t s0, int32_t s1, int32_t* urow_h, int32_t* urow_m) {
+    if (!tok_off || !len || !mask || !mask_end || !urow_h || !urow_m) return fail(RS_EARG, "null argument");
+    if (s0 < 0 || s1 <= s0 || s1 > n_seq) return fail(RS_EARG, "bad sequence range");
+    SeqList sl;
+    for (int s = 0; s < n_seq; ++s) sl.push(tok_off[s], len[s], mask[s], mask_end[s], 0, -1);
+    const int urows = plan_unique_rows(sl, s0, s1);
+    for (int s = s0; s < s1 && urows > 0; ++s) {
+        urow_h[s] = sl.urow_h[s];
+        urow_m[s] = sl.urow_m[s];
+    }
+    return urows;
+}
+
 int rs_model_set_token_types(rs_model* m, const int32_t* d_type, int64_t n) {
     if (!m) return fail(RS_EARG, "null model");
     if (d_type && n < 0) return fail(RS_EARG, "negative count");
