@@ -150,6 +150,8 @@ _DEBUG_SIGS = {
     "rs_debug_decoder_topk": (CI, [P, P, P, P, CI, CI, CI, CI, CI, P, P, P, P, CI, P, P, P, P]),
     # (qkv, qkv32, len, row, query, s0, s1, row0, H, heads, kx, qd, x32, stats, g, b, himg, ctxq, resq, stream)
     "rs_debug_attention_query": (CI, [P, CI, P, P, P, CI, CI, CI, CI, CI, CI, P, P, P, P, P, P, P, P, P]),
+    # (himg, tq, wkf, wvt, bv, len, row, query, s0, s1, row0, H, heads, kx, work, work_bytes, ctxq, resq, stream)
+    "rs_debug_attention_fold": (CI, [P, P, P, P, P, P, P, P, CI, CI, CI, CI, CI, CI, P, ctypes.c_longlong, P, P, P]),
     # (form, qkv, seq_off, klen, n_seq, H, heads, dctx, seed, step, site, p, ctx, dqkv, stream)
     "rs_debug_train_attn": (CI, [CI, P, P, P, CI, CI, CI, P, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32,
                                  ctypes.c_float, P, P, P]),

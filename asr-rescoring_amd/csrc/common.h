@@ -268,6 +268,54 @@ hipError_t launch_attention_query(const void* qkv, bool qkv32, const float* x32,
                                   const float* g, const float* b, SeqMeta sm, int s0, int s1,
                                   int row0, int H, int heads, f16* ctxq, float* resq, int kx,
                                   hipStream_t st, const void* qd = nullptr, const f16* himg = nullptr);
+// The folded last-layer attention of the scored rows (k_attn.hip, RS_LASTFOLD): the K / V
+// projections applied to the query side, so that no K / V row is projected.  Over sequences
+// [s0, s1): himg the two-part image [rows, 2H] of the layer's input (row = sm.row[s] - row0 + t), tq
+// the dense Q [s1 - s0, H]; weight images (fp32, built once at finalize): wkf [H, H] = Wk / 8 (row
+// 64 h + d: head h's key weights, the softmax scale folded in), wvt [H, H] = Wv transposed
+// (wvt[j][c] = Wv[c][j]), bv [H].  work: scratch for G and U, 2 * heads * H floats per sequence of a
+// batch; the launcher cuts [s0, s1) into as many batches as work_bytes asks for (one, when
+// work_bytes >= (s1 - s0) * heads * H * 8).  ctxq: the kx = 1 or 3 operand image, resq = hi + lo/64
+// of the scored row's image.  H = 64 heads, H % 256 == 0, H <= 1024 (attention_fold_ok).
+struct AttnFold {
+    const f16* himg;
+    const float *tq, *wkf, *wvt, *bv;
+    SeqMeta sm;
+    int s0, s1, row0, H, heads, kx;
+    void* work;
+    size_t work_bytes;
+    f16* ctxq;
+    float* resq;
+};
+bool attention_fold_ok(int H, int heads);
+// dst[s - s0] = the first H floats of src's row at sequence s's query position (fp32 rows of ld floats):
+// the scored rows' Q out of a full Q/K/V GEMM's output (RS_LASTQ=0 with the folded last layer)
+hipError_t launch_gather_q32(const float* src, int ld, SeqMeta sm, int s0, int s1, int row0, int H, float* dst,
+                             hipStream_t st);
+// one batch [s0, s0 + n) of a's sequences: G = tq . Wk_h / 8 per head; softmax and U; ctxq = U . Wv_h^T + bv
+hipError_t launch_fold_in(const AttnFold& a, int s0, int n, float* G, hipStream_t st);
+hipError_t launch_fold_query(const AttnFold& a, int s0, int n, const float* G, float* U, hipStream_t st);
+hipError_t launch_fold_out(const AttnFold& a, int s0, int n, const float* U, hipStream_t st);
+// wrap(kind, flops, launch): kind 0 = a fold GEMM (flops = its 2 M N K), 1 = the query kernel; runs
+// one launch and returns its error (the scorer's profiler scopes, or a plain call)
+template <class Wrap>
+hipError_t launch_attention_fold(const AttnFold& a, hipStream_t st, Wrap&& wrap) {
+    if (a.s1 <= a.s0) return hipSuccess;
+    if (!attention_fold_ok(a.H, a.heads)) return hipErrorInvalidValue;
+    const size_t per = (size_t)a.heads * a.H;                 // floats of G (and of U) per sequence
+    const size_t cap = a.work_bytes / (2 * per * sizeof(float));
+    if (cap == 0) return hipErrorInvalidValue;
+    for (int s = a.s0; s < a.s1;) {
+        const int n = (int)(cap < (size_t)(a.s1 - s) ? cap : (size_t)(a.s1 - s));
+        float *G = (float*)a.work, *U = G + (size_t)n * per;
+        const double flops = 2.0 * n * (double)a.H * a.H;
+        if (hipError_t e = wrap(0, flops, [&] { return launch_fold_in(a, s, n, G, st); })) return e;
+        if (hipError_t e = wrap(1, 0.0, [&] { return launch_fold_query(a, s, n, G, U, st); })) return e;
+        if (hipError_t e = wrap(0, flops, [&] { return launch_fold_out(a, s, n, U, st); })) return e;
+        s += n;
+    }
+    return hipSuccess;
+}
 // dst[s - s0] = src[row of sequence s's query position], ld halfs per row
 hipError_t launch_gather_query_rows(const f16* src, int ld, SeqMeta sm, int s0, int s1, int row0, f16* dst,
                                    hipStream_t st);

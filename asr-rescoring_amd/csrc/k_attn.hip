@@ -744,6 +744,200 @@ attn_mquery_kernel(const QT* __restrict__ qkv, const QT* __restrict__ qd, const 
     }
 }
 
+// ---- folded last layer (RS_LASTFOLD): K / V projections applied to the query side -------------
+// K_i = Wk x_i + bk and V_i = Wv x_i + bv are linear in the layer's input rows x_i, and only one
+// query row per sequence reads them, so per (sequence, head h)
+//   s_i  = q_h . K_i,h / 8 = g_h . x_i + const,   g_h = Wk_h^T q_h / 8   (the constant q_h . bk_h / 8
+//                                                  does not depend on i and cancels in the softmax)
+//   ctx_h = sum_i p_i V_i,h = Wv_h u_h + bv_h,     u_h = sum_i p_i x_i    (sum_i p_i = 1)
+// Three launches: fold_gemm_kernel<false> (G = the g_h of every sequence), attn_fold_kernel
+// (softmax and U = the u_h over the two-part image of x), fold_gemm_kernel<true> (ctxq).  No
+// K / V row of the chunk is projected.
+
+// Batched fp32 GEMM of the two folds on the f32-input MFMA (exact fp32: every element a fixed-order
+// fmaf chain): batch b = blockIdx.z, C_b[M, N] = A_b[M, K] . B_b[K, N], A_b = A + b a_bs rows of lda
+// floats (k contiguous), B_b = B + b b_bs rows of ldb floats (n contiguous).  One wave per
+// 32 x 64 output tile, four independent waves (row tiles) per workgroup, operands straight from
+// global memory into the MFMA fragments: MFMA step kk of a 32-deep K-step takes k = 16 (lane >> 5)
+// + kk on both operands, so a lane's 16 A values are 64 contiguous bytes and a half-wave's B values
+// of one step 128.  K % 32 == 0, N % 64 == 0 (grid.y = N / 64), rows >= M load row M - 1 and are not
+// stored.  IMG: N = 64, C_b + bias[64 b + n] goes to columns 64 b + n of the kx operand image
+// img [M, kx Himg] (put_split); else C_b = C + b c_bs, rows of ldc floats.
+template <bool IMG>
+__global__ void __launch_bounds__(256)
+fold_gemm_kernel(const float* __restrict__ A, int lda, int a_bs, const float* __restrict__ B, int ldb, int b_bs,
+                 int M, int K, float* __restrict__ C, int ldc, int c_bs, const float* __restrict__ bias,
+                 f16* __restrict__ img, int Himg, int kx) {
+    const int lane = threadIdx.x & 63, h = lane >> 5, c = lane & 31;
+    const int m0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 32, n0 = blockIdx.y * 64, b = blockIdx.z;
+    if (m0 >= M) return;                          // (no barrier in this kernel)
+    const float* ap = A + (size_t)b * a_bs + (size_t)min(m0 + c, M - 1) * lda + 16 * h;
+    const float* bp = B + (size_t)b * b_bs + (size_t)(16 * h) * ldb + n0 + c;
+    f32x16 acc[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+    for (int k0 = 0; k0 < K; k0 += 32) {
+        float fa[16], fb[2][16];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float4 v = *(const float4*)(ap + k0 + 4 * q);
+            fa[4 * q] = v.x; fa[4 * q + 1] = v.y; fa[4 * q + 2] = v.z; fa[4 * q + 3] = v.w;
+        }
+#pragma unroll
+        for (int kk = 0; kk < 16; ++kk) {
+            const float* br = bp + (size_t)(k0 + kk) * ldb;
+            fb[0][kk] = br[0];
+            fb[1][kk] = br[32];
+        }
+#pragma unroll
+        for (int kk = 0; kk < 16; ++kk)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[kk], fb[j][kk], acc[j], 0, 0, 0);
+    }
+    // D map of the 32x32 MFMA: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int col = n0 + 32 * j + c;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = m0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+            if (row >= M) continue;
+            if constexpr (IMG) put_split(img + (size_t)row * kx * Himg, 64 * b + col, Himg, kx, acc[j][r] + bias[64 * b + col]);
+            else C[(size_t)b * c_bs + (size_t)row * ldc + col] = acc[j][r];
+        }
+    }
+}
+
+// Folded last-layer attention of the scored row: one workgroup per sequence, wave h = head h
+// (H = 256 NK, 4 NK heads of 64), over the two-part image himg of the layer's input rows.  The
+// sequence's rows are staged ONCE for all heads, R at a time, as fp32 hi + lo/64 in LDS; per tile a
+// wave forms s_i = g_h . x_i (lane l holds columns 256 k + 4 l .. + 3, k < NK, of g_h, x_i and u_h;
+// 4 NK fmaf per lane in a fixed order, then the wave's butterfly sum; lane i keeps s_i), the
+// max-shifted probabilities and u_h += p_i x_i, with attn_full_kernel's online rescaling from tile
+// to tile (any T; nothing but the trip count depends on it).  No atomics; every sum has one fixed
+// order, so the result is the same bits on every run.  U row (s - s0) * heads + h = u_h / l; resq
+// as attn_query_kernel forms it from the image.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+// Sum over the wave on the DPP network (no LDS traffic, unlike the shuffles of wave_sum): pairs,
+// quads, the 16-lane row (rotations by 4 and 8: every lane of a row then holds the row's sum), rows
+// 0 + 1 and 2 + 3 (row_bcast:15 into rows 1 and 3), both pairs (row_bcast:31 into rows 2 and 3); the
+// total stands in lane 63 and comes back as a scalar.  Masked rows add 0 (old = 0).
+template <int CTRL, int ROWS>
+__device__ __forceinline__ float dpp_add(float v) {
+    return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROWS, 0xF, false));
+}
+__device__ __forceinline__ float wave_sum_dpp(float v) {
+    v = dpp_add<0xB1, 0xF>(v);      // quad_perm [1, 0, 3, 2]
+    v = dpp_add<0x4E, 0xF>(v);      // quad_perm [2, 3, 0, 1]
+    v = dpp_add<0x124, 0xF>(v);     // row_ror:4
+    v = dpp_add<0x128, 0xF>(v);     // row_ror:8
+    v = dpp_add<0x142, 0xA>(v);     // row_bcast:15
+    v = dpp_add<0x143, 0xC>(v);     // row_bcast:31
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
+}
+constexpr int FOLD_R = 24;      // staged rows per tile: R H 4 B of LDS (H 768: 72 KiB, two workgroups per CU)
+template <int NK>
+__global__ void __launch_bounds__(256 * NK, NK <= 3 ? 2 * NK : NK)     // two workgroups per CU where the LDS holds two
+attn_fold_kernel(const f16* __restrict__ himg, const float* __restrict__ G, float* __restrict__ U,
+                 float* __restrict__ resq, SeqMeta sm, int s0, int row0) {
+    constexpr int H = 256 * NK, NT = 256 * NK, R = FOLD_R;
+    __shared__ __attribute__((aligned(16))) float sx[R][H];
+    const int s = s0 + blockIdx.x, s_loc = blockIdx.x;
+    const int T = sm.len[s], rs = sm.row[s] - row0, qi = sm.query[s];
+    const int tid = threadIdx.x, lane = tid & 63, hd = tid >> 6;
+    const f16* img = himg + (size_t)rs * 2 * H;
+    const size_t gu = ((size_t)s_loc * (4 * NK) + hd) * H + 4 * lane;
+    f32x4 g[NK], u[NK];
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+        g[k] = *(const f32x4*)(G + gu + 256 * k);
+        u[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    float m = -INFINITY, l = 0.f;
+    for (int t0 = 0; t0 < T; t0 += R) {
+        const int nk = min(R, T - t0);
+        // stage rows [t0, t0 + R) (zeros past the sequence's end, so that the row loops below run in
+        // whole groups of four): a thread takes 8 columns (one half8 of hi, one of lo) of R / 8 rows
+        half8 vh[R / 8], vl[R / 8];
+#pragma unroll
+        for (int i = 0; i < R / 8; ++i) {
+            const int un = tid + i * NT, r = un / (H / 8), c8 = (un % (H / 8)) * 8;
+            vh[i] = vl[i] = half8{0, 0, 0, 0, 0, 0, 0, 0};
+            if (r < nk) {
+                const f16* p = img + (size_t)(t0 + r) * 2 * H + il_hi(c8);
+                vh[i] = *(const half8*)p;
+                vl[i] = *(const half8*)(p + 32);
+            }
+        }
+        __syncthreads();                          // the previous tile's readers are done
+#pragma unroll
+        for (int i = 0; i < R / 8; ++i) {
+            const int un = tid + i * NT, r = un / (H / 8), c8 = (un % (H / 8)) * 8;
+            float x[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) x[e] = (float)vh[i][e] + (float)vl[i][e] * X3_DOWN;
+            *(float4*)&sx[r][c8] = make_float4(x[0], x[1], x[2], x[3]);
+            *(float4*)&sx[r][c8 + 4] = make_float4(x[4], x[5], x[6], x[7]);
+        }
+        __syncthreads();
+        // scores, four rows at a time (independent chains): two packed fmaf accumulators per row, then
+        // the wave's sum on the DPP network (wave_sum_dpp: one fixed order)
+        float sc = -INFINITY;
+        for (int r0 = 0; r0 < nk; r0 += 4) {
+            float d[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                f32x2 a = {0.f, 0.f};
+#pragma unroll
+                for (int k = 0; k < NK; ++k) {
+                    const f32x4 x = *(const f32x4*)&sx[r0 + j][256 * k + 4 * lane];
+                    a = __builtin_elementwise_fma(g[k].xy, x.xy, a);
+                    a = __builtin_elementwise_fma(g[k].zw, x.zw, a);
+                }
+                d[j] = a.x + a.y;
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float t = wave_sum_dpp(d[j]);
+                if (lane == r0 + j) sc = t;
+            }
+        }
+        if (lane >= nk) sc = -INFINITY;           // (the zero rows past the end scored 0)
+        const float mn = fmaxf(m, wave_max(sc));
+        const float p = lane < nk ? __expf(sc - mn) : 0.f;
+        const float alpha = __expf(m - mn);       // m = -inf on the first tile -> 0
+        l = l * alpha + wave_sum(p);
+#pragma unroll
+        for (int k = 0; k < NK; ++k) u[k] *= alpha;
+        for (int r0 = 0; r0 < nk; r0 += 4) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                // p of row r0 + j to every lane (the row index is the wave's: a scalar lane read)
+                const float pr = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, p), r0 + j));
+                const f32x2 pp = {pr, pr};
+#pragma unroll
+                for (int k = 0; k < NK; ++k) {
+                    const f32x4 x = *(const f32x4*)&sx[r0 + j][256 * k + 4 * lane];
+                    u[k].xy = __builtin_elementwise_fma(pp, x.xy, u[k].xy);
+                    u[k].zw = __builtin_elementwise_fma(pp, x.zw, u[k].zw);
+                }
+            }
+        }
+        m = mn;
+    }
+#pragma unroll
+    for (int k = 0; k < NK; ++k)
+        *(f32x4*)(U + gu + 256 * k) = f32x4{u[k].x / l, u[k].y / l, u[k].z / l, u[k].w / l};
+    {   // residual of the scored row: the normalised state's image
+        const int c = hd * 64 + lane;
+        const float2 hl = il_parts(img + (size_t)qi * 2 * H, c);
+        resq[(size_t)s_loc * H + c] = hl.x + hl.y * X3_DOWN;
+    }
+}
+
 // Diagnostic: the memory skeleton of attn_tr_kernel (same Q/K/V reads per (sequence, head)
 // wave, ctx written) with no math — the access pattern's own cost.
 __global__ void __launch_bounds__(256)
@@ -837,6 +1031,78 @@ hipError_t launch_attention_mquery(const void* qkv, bool qkv32, const float* x32
     else
         hipLaunchKernelGGL(attn_mquery_kernel<f16>, grid, dim3(256), 0, st, (const f16*)qkv, (const f16*)qd, x32, stats, g, b, sm, qm, s0, H, ctxq, resq, kx, himg);
     return hipGetLastError();
+}
+
+namespace {
+// dst[s - s0][0, H) = src[row of sequence s's query position][0, H), fp32 rows of ld floats (H % 4 == 0)
+__global__ void __launch_bounds__(64)
+gather_q32_kernel(const float* __restrict__ src, int ld, SeqMeta sm, int s0, int row0, int H, float* __restrict__ dst) {
+    const int s = s0 + blockIdx.x;
+    const size_t r = (size_t)(sm.row[s] - row0 + sm.query[s]);
+    const float4* a = (const float4*)(src + r * ld);
+    float4* o = (float4*)(dst + (size_t)blockIdx.x * H);
+    for (int i = threadIdx.x; i < H / 4; i += 64) o[i] = a[i];
+}
+}  // namespace
+
+hipError_t launch_gather_q32(const float* src, int ld, SeqMeta sm, int s0, int s1, int row0, int H, float* dst,
+                             hipStream_t st) {
+    if (s1 <= s0) return hipSuccess;
+    if (H % 4 || ld % 4) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gather_q32_kernel, dim3(s1 - s0), dim3(64), 0, st, src, ld, sm, s0, row0, H, dst);
+    return hipGetLastError();
+}
+
+bool attention_fold_ok(int H, int heads) { return H == heads * 64 && H % 256 == 0 && H <= 1024; }
+
+hipError_t launch_fold_in(const AttnFold& a, int s0, int n, float* G, hipStream_t st) {
+    const int H = a.H;
+    hipLaunchKernelGGL(fold_gemm_kernel<false>, dim3((n + 127) / 128, H / 64, a.heads), dim3(256), 0, st,
+                       a.tq + (size_t)(s0 - a.s0) * H, H, 64, a.wkf, H, 64 * H, n, 64, G, a.heads * H, H, nullptr,
+                       nullptr, 0, 0);
+    return hipGetLastError();
+}
+
+hipError_t launch_fold_query(const AttnFold& a, int s0, int n, const float* G, float* U, hipStream_t st) {
+    float* resq = a.resq + (size_t)(s0 - a.s0) * a.H;
+    switch (a.H / 256) {
+        case 1: hipLaunchKernelGGL(attn_fold_kernel<1>, dim3(n), dim3(256), 0, st, a.himg, G, U, resq, a.sm, s0, a.row0); break;
+        case 2: hipLaunchKernelGGL(attn_fold_kernel<2>, dim3(n), dim3(512), 0, st, a.himg, G, U, resq, a.sm, s0, a.row0); break;
+        case 3: hipLaunchKernelGGL(attn_fold_kernel<3>, dim3(n), dim3(768), 0, st, a.himg, G, U, resq, a.sm, s0, a.row0); break;
+        case 4: hipLaunchKernelGGL(attn_fold_kernel<4>, dim3(n), dim3(1024), 0, st, a.himg, G, U, resq, a.sm, s0, a.row0); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_fold_out(const AttnFold& a, int s0, int n, const float* U, hipStream_t st) {
+    const int H = a.H;
+    hipLaunchKernelGGL(fold_gemm_kernel<true>, dim3((n + 127) / 128, 1, a.heads), dim3(256), 0, st, U, a.heads * H, H,
+                       a.wvt, H, 64, n, H, nullptr, 0, 0, a.bv, a.ctxq + (size_t)(s0 - a.s0) * a.kx * H, H, a.kx);
+    return hipGetLastError();
+}
+
+// Test entry (not part of the scoring path): the folded last-layer attention through the production
+// launcher (launch_attention_fold) over sequences [s0, s1) of the device metadata arrays len / row /
+// query.  himg: the two-part image [rows, 2H] of the layer's input, row index = row[s] - row0 + t;
+// tq: the dense Q [s1 - s0, H] (bias included); wkf / wvt / bv: the fold's weight images as
+// rs_model_finalize builds them (wkf = Wk / 8, wvt = Wv transposed, bv the V bias; fp32); work:
+// work_bytes of scratch for G and U (a small one makes the launcher run in several batches); ctxq
+// the kx = 1 or 3 image [s1 - s0, kx H], resq fp32 [s1 - s0, H].
+extern "C" int rs_debug_attention_fold(const void* himg, const float* tq, const float* wkf, const float* wvt,
+                                       const float* bv, const int* len, const int* row, const int* query, int s0,
+                                       int s1, int row0, int H, int heads, int kx, void* work, long long work_bytes,
+                                       void* ctxq, float* resq, void* stream) {
+    if (!himg || !tq || !wkf || !wvt || !bv || !len || !row || !query || !work || !ctxq || !resq) return -1;
+    if (s0 < 0 || s1 <= s0 || work_bytes <= 0 || !attention_fold_ok(H, heads) || (kx != 1 && kx != 3)) return -1;
+    AttnFold a{};
+    a.himg = (const f16*)himg; a.tq = tq; a.wkf = wkf; a.wvt = wvt; a.bv = bv;
+    a.sm.len = len; a.sm.row = row; a.sm.query = query;
+    a.s0 = s0; a.s1 = s1; a.row0 = row0; a.H = H; a.heads = heads; a.kx = kx;
+    a.work = work; a.work_bytes = (size_t)work_bytes; a.ctxq = (f16*)ctxq; a.resq = resq;
+    hipStream_t st = (hipStream_t)stream;
+    const hipError_t e = launch_attention_fold(a, st, [](int, double, auto&& launch) { return launch(); });
+    return e == hipSuccess ? 0 : -2;
 }
 
 // Timing/diagnostic entry (not part of the scoring path): one attention launch over

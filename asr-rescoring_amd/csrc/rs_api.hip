@@ -32,6 +32,8 @@ struct Layer {
     f16 *iqkv = nullptr, *io = nullptr, *i1 = nullptr, *i2 = nullptr;   // fp16x3: interleaved two-part
                                     // images [W_hi | W_lo*64] of the split-operand GEMMs (ldw = 2K)
     float *bqkv, *bo, *b1, *b2, *g1, *be1, *g2, *be2;
+    float *wkf = nullptr, *wvt = nullptr;   // last layer, fp16x3: fp32 weight images of the folded
+                                    // attention (common.h AttnFold: Wk / 8, Wv transposed)
 };
 
 // Pinned staging buffer (int words) of one asynchronous upload per call: the next call waits for
@@ -429,6 +431,7 @@ struct Call {
 // forms.  Read per call, not once per process, so that a test can flip a switch in-process.
 struct CallOpts {
     bool lastq, dedup, chunk_align;
+    bool lastfold;                        // the last layer's K / V projections folded into the query side
     int ln_diag;
     // the layer forms that run, resolved against the model's precision mode, weights and shape
     bool x3s, imgres, lnfuse, x3_dedup;   // fp16x3
@@ -481,6 +484,14 @@ CallOpts call_opts(const rs_model* m) {
     // fp16x3 layer-0 dedup: the split-operand layer with the image-held residual (its attention
     // kernel reads the unique rows for chunks with T <= 64)
     o.x3_dedup = o.imgres;
+    // RS_LASTFOLD (default 1; split-operand layers with the image-held residual, single-query
+    // sequences): the last layer applies its K / V projections to the query side
+    // (launch_attention_fold) instead of projecting K and V for every row; 0 = the all-rows K / V GEMM
+    // and attention_query.  Independent of RS_LASTQ, which only says where the scored rows' Q comes
+    // from (their own GEMM, or the Q columns of the full Q/K/V GEMM: the same bits), so the default and
+    // RS_LASTQ=0 stay bitwise equal.
+    o.lastfold = o.imgres && !is("RS_LASTFOLD", "0") && attention_fold_ok(cf.hidden, cf.heads) &&
+                 !m->layers.empty() && m->layers.back().wkf != nullptr;
     return o;
 }
 
@@ -588,8 +599,11 @@ struct ChunkCtx {
         // K and V for every row (rows H..3H of the fused weight, written into columns H..3H of
         // qkv), Q only for the scored row(s) of each sequence (gathered operand rows -> dense
         // [sequence or query, H] in the idle tq32 buffer)
-        if (int r = gemm(RS_K_QKV, qkv_epi, sp, h16, W + (size_t)H * ldw, rows, 2 * H, K,
-                         bias_ep(L.bqkv + H, (char*)qkv + H * (size_t)(q32 ? 4 : 2), 3 * H), 2 * H)) return r;
+        // (folded last layer: no K / V row is projected, layer_query applies Wk and Wv to the query side)
+        if (!fold()) {
+            if (int r = gemm(RS_K_QKV, qkv_epi, sp, h16, W + (size_t)H * ldw, rows, 2 * H, K,
+                             bias_ep(L.bqkv + H, (char*)qkv + H * (size_t)(q32 ? 4 : 2), 3 * H), 2 * H)) return r;
+        }
         if (mq) LAUNCH_OTHER(launch_gather_query_rows_list(h16, kxf * H, sm, qm, c.q0, c.nq, hq16, st));
         else LAUNCH_OTHER(launch_gather_query_rows(h16, kxf * H, sm, c.s0, c.s1, 0, hq16, st));
         return gemm(RS_K_QKV, qkv_epi, sp, hq16, W, nr, H, K, bias_ep(L.bqkv, tq, H), H);
@@ -670,10 +684,30 @@ struct ChunkCtx {
         return RS_OK;
     }
 
+    // The last layer (layer_query) runs folded (CallOpts.lastfold): single-query calls
+    bool fold() const { return o.lastfold && !mq; }
+    // Folded attention of the scored rows: G and U live in the QKV buffer, dead in this layer.  The
+    // two fold GEMMs count as qkv (2 M N K each), the query kernel as attn.
+    int attention_fold(const Layer& L) {
+        AttnFold a{};
+        a.himg = h16; a.tq = tq; a.wkf = L.wkf; a.wvt = L.wvt; a.bv = L.bqkv + 2 * H;
+        a.sm = sm; a.s0 = c.s0; a.s1 = c.s1; a.row0 = 0; a.H = H; a.heads = nh; a.kx = kx;
+        a.work = qkv; a.work_bytes = m->qkv.bytes; a.ctxq = ctxq; a.resq = resq;
+        TRY_HIP(launch_attention_fold(a, st, [&](int kind, double flops, auto&& launch) {
+            ProfScope ps(m, st, kind == 0 ? RS_K_QKV : RS_K_ATTN, flops);
+            return launch();
+        }));
+        return RS_OK;
+    }
+
     // Last layer of the scoring modes: only the scored rows (one per sequence, or one per query)
     int layer_query(int li, bool qrow) {
         const Layer& L = m->layers[li];
-        if (mq)
+        if (fold()) {
+            // RS_LASTQ=0: the scored rows' Q out of the full Q/K/V GEMM's output, which is dead from then on
+            if (!qrow) LAUNCH_OTHER(launch_gather_q32((const float*)qkv, 3 * H, sm, c.s0, c.s1, 0, H, tq, st));
+            if (int r = attention_fold(L)) return r;
+        } else if (mq)
             LAUNCH(RS_K_ATTN, launch_attention_mquery(qkv, q32, t32, xst, prev_g(li), prev_b(li), sm, qm, c.s0, c.s1, H, nh,
                                                       ctxq, resq, kx, st, qrow ? tq : nullptr, o.imgres ? h16 : nullptr));
         else
@@ -1113,6 +1147,18 @@ int rs_model_finalize(rs_model* m) {
         UP32(L.b2, b2, H);
         UP32(L.g2, g2, H);
         UP32(L.be2, be2, H);
+        if (x3s_w && i == c.layers - 1 && attention_fold_ok((int)H, c.heads)) {
+            // folded last-layer attention (RS_LASTFOLD): Wk / 8 (exact: the softmax scale of head_dim 64)
+            // and Wv transposed, fp32
+            std::vector<float> wkf(H * H), wvt(H * H);
+            for (size_t r = 0; r < H; ++r)
+                for (size_t j = 0; j < H; ++j) {
+                    wkf[r * H + j] = (*wk)[r * H + j] * 0.125f;
+                    wvt[j * H + r] = (*wv)[r * H + j];
+                }
+            UP32(L.wkf, &wkf, H * H);
+            UP32(L.wvt, &wvt, H * H);
+        }
         if (x3s_w) {
             UPIL(L.iqkv, &wqkv, H);
             UPIL(L.io, wo, H);
