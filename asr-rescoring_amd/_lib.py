@@ -110,6 +110,9 @@ _SIGS = {
     "rs_trainer_destroy": (None, [P]),
     "rs_bertscore_recall": (ctypes.c_int, [P, P, P, P, I32, P, P, P]),
     "rs_align": (ctypes.c_int, [P, P, P, P, I32, P, P, P, P, P, P, P, I32, P]),
+    "rs_cn_merge": (ctypes.c_int, [P, P, P, P, P, P, I32, I32, P, P, P, P, P, P, I64, I32, P]),
+    "rs_cn_oracle": (ctypes.c_int, [P, P, P, P, P, P, I32, I32, P, P, I32, P, P, P, P, P]),
+    "rs_cn_vote": (ctypes.c_int, [P, P, P, P, P, P, I32, I32, P, P, P, P, P, P, P]),
     "rs_fuse_rerank": (ctypes.c_int, [P, P, P, P, I32, I32, P, I32, I32, P, P]),
     "rs_corpus_edits": (ctypes.c_int, [P, P, P, I32, I32, P, P]),
     "rs_ref_edit": (ctypes.c_int, [P, P, P, P, P, I32, P, P]),

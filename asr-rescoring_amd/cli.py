@@ -7,6 +7,8 @@
   python -m asr_rescoring_amd.cli rescorebert_train --config MD.yaml # RescoreBert/main.py (task: train)
   python -m asr_rescoring_amd.cli rescore     --config rescore.yaml  # rescore.py
   python -m asr_rescoring_amd.cli rmbr        --config CER.yaml      # RMBR/main.py (utility: cer / bertscore)
+  python -m asr_rescoring_amd.cli nbest_align --config align.yaml    # Nbest_Align/preprocess.py (features + oracle)
+  python -m asr_rescoring_amd.cli consensus   --config rescore.yaml  # confusion-network consensus decode
 
 Differences forced by the offline image (no model hub): ``model.bert`` cannot be fetched,
 so weights come from ``checkpoint_path`` (an HF-keyed state_dict, loaded with
@@ -686,6 +688,78 @@ def rmbr(cfg) -> Dict[str, float]:
     return res
 
 
+def nbest_align(cfg) -> Dict[str, Dict[str, float]]:
+    """Nbest_Align/preprocess.py:67-159 (get_feature) for every ``{split}_feature`` / ``{split}_feature_path``
+    the config has (features ``ref_text`` and ``hyp_text``; ``n_best``, ``max_utt``): the slot table in the
+    reference's form (``cnet_mode: reference``, the default here) with the DP oracle's labels.  Writes
+    ``{split}_features.json`` (the rows) and ``{split}_oracle.json`` (token-level oracle distance per
+    utterance and the corpus confusion-network oracle CER = sum of distances / sum of transcript tokens)."""
+    from . import cnet
+    os.makedirs(cfg.output_path, exist_ok=True)
+    n_best, max_utt = int(get(cfg, "n_best", 1 << 30)), int(get(cfg, "max_utt", 1 << 30))
+    mode = str(get(cfg, "cnet_mode", "reference"))
+    res, tok = {}, None
+    for split in ("train", "dev", "test"):
+        feats, paths = get(cfg, f"{split}_feature"), get(cfg, f"{split}_feature_path")
+        if not feats or not paths:
+            continue
+        refs, hyps = _load(paths[feats.index("ref_text")]), _load(paths[feats.index("hyp_text")])
+        uids = list(refs)[:max_utt]
+        if tok is None:
+            tok = _tokenizer(cfg, [t for h in hyps.values() for t in h.values()] + list(refs.values()) + [cnet.GAP])
+        lists = [[tok.tokenize(t) for t in list(hyps[u].values())[:n_best]] for u in uids]
+        ref_tok = [tok.tokenize(refs[u]) for u in uids]
+        table = cnet.merge_nbest(lists, mode=mode, device=_dev(cfg))
+        dist, labels = table.oracle(ref_tok)
+        rows = cnet.align_features(table, labels, tok, utt_ids=uids)
+        total = sum(len(r) for r in ref_tok)
+        oracle_cer = float(dist.sum()) / total if total else 0.0
+        D.json_saving(os.path.join(cfg.output_path, f"{split}_features.json"), rows)
+        D.json_saving(os.path.join(cfg.output_path, f"{split}_oracle.json"),
+                      {"oracle_dist": {u: int(d) for u, d in zip(uids, dist)}, "oracle_cer": oracle_cer})
+        print(f"{split} confusion-network oracle cer: ", oracle_cer)
+        res[split] = {"oracle_cer": oracle_cer, "n_utt": len(uids)}
+    if not res:
+        raise ValueError("nbest_align: no {train,dev,test}_feature / _feature_path in the config")
+    return res
+
+
+def consensus(cfg) -> Dict[str, float]:
+    """The inputs of ``rescore``; the confusion-network consensus decode (rerank.find_best_weight_consensus:
+    best weight on dev, CER on test) next to the argmax rerank's.  Extra keys: ``consensus_scale`` (1.0),
+    ``cnet_mode`` (exact).  Logged to output_path/consensus.log, returned and written to consensus.json."""
+    from . import rerank
+    os.makedirs(cfg.output_path, exist_ok=True)
+    log = _logger(os.path.join(cfg.output_path, "consensus.log"))
+    log.info(str(cfg))
+    n_best, dev_id = cfg.n_best, _dev(cfg)
+    scale, mode = float(get(cfg, "consensus_scale", 1.0)), str(get(cfg, "cnet_mode", "exact"))
+
+    def split_nb(prefix):
+        hyps = _load(getattr(cfg, f"{prefix}_hyps_text_path"))
+        lm_j = _load(getattr(cfg, f"{prefix}_lm_path"))
+        nb = D.from_texts(hyps, _load(getattr(cfg, f"{prefix}_ref_text_path")),
+                          _load(getattr(cfg, f"{prefix}_am_path")), n_best=n_best)
+        return nb, np.asarray([lm_j[u][h] for u in nb.utt_ids for h in list(lm_j[u])[:n_best]], np.float64)
+
+    dev_nb, dev_lm = split_nb("dev")
+    arg_w, arg_cer, _, _ = rerank.find_best_weight(dev_nb, dev_lm, n_best=n_best, mode="norm", device=dev_id)
+    best_w, best_cer, _ = rerank.find_best_weight_consensus(dev_nb, dev_lm, n_best, scale, mode, dev_id)
+    test_nb, test_lm = split_nb("test")
+    arg = rerank.fuse_rerank(test_nb.am, test_lm, test_nb.hyp_len(), test_nb.utt_off, [arg_w], "norm", n_best,
+                             device=dev_id)
+    edits = rerank.corpus_edits(rerank.ref_edits(test_nb, device=dev_id), test_nb.utt_off, arg).cpu().numpy()[0]
+    res = {"best_weight": best_w, "dev_cer": best_cer,
+           "test_cer": rerank.consensus_decode(test_nb, test_lm, best_w, scale, n_best, mode, dev_id)[0],
+           "argmax_best_weight": arg_w, "argmax_dev_cer": arg_cer,
+           "argmax_test_cer": float(edits) / sum(len(r) for r in test_nb.refs)}
+    for k, v in res.items():
+        log.info(f"{k}: {v}")
+        print(f"{k}: ", v)
+    D.json_saving(os.path.join(cfg.output_path, "consensus.json"), res)
+    return res
+
+
 def _dev(cfg) -> int:
     d = str(get(cfg, "device", "cuda:0"))
     return int(d.split(":")[1]) if ":" in d else 0
@@ -702,7 +776,7 @@ def _logger(path):
 
 COMMANDS = {"mlm_pll": mlm_pll, "mlm_topk": mlm_topk, "mlm_finetune": mlm_finetune, "rescorebert": rescorebert,
             "rescorebert_train": rescorebert_train,
-            "rescore": rescore, "rmbr": rmbr}
+            "rescore": rescore, "rmbr": rmbr, "nbest_align": nbest_align, "consensus": consensus}
 
 
 def main(argv=None):

@@ -9,6 +9,9 @@ Host mirrors of the reference functions (same names, argument meaning, tie rules
 * ``fuse_rerank`` — ``rescore`` + ``get_highest_score_hyp`` (rescore.py:47-58).
 * ``mbr_decode`` / ``find_best_length`` — RMBR/mbr.py:5-28, RMBR/main.py:15-35 with
   ``CerScoreFunction``; the pairwise edit matrix is computed once and reused for every k.
+* ``consensus_decode`` / ``find_best_weight_consensus`` — no reference counterpart: the per-slot vote
+  over the N-best confusion network (``cnet``), every hypothesis weighted by the softmax of the fused
+  score, scored by the same CER kernels; a third decoding rule beside argmax and MBR.
 
 Inputs are ``NBest`` (token/char ids); "characters" are symbols, as jiwer's CER splits text
 into characters (CJK: one token per character).
@@ -171,6 +174,79 @@ def find_best_length(nb: NBest, n_best: int, device=0) -> Tuple[float, int, np.n
         if err < best_cer:
             best_cer, best_len, best_sc = err, k, sc
     return best_cer, best_len, best_sc
+
+
+class _Consensus:
+    """A slot table of the first ``n_best`` hypotheses per utterance plus what scoring its decodes needs."""
+
+    def __init__(self, nb: NBest, n_best: int, mode: str, device):
+        from . import cnet
+        if any(len(r) == 0 for r in nb.refs):
+            raise ValueError("one or more references are empty strings")   # jiwer behaviour
+        self.nb, self.cnet = nb, cnet
+        keep = [np.arange(a, min(b, a + n_best)) for a, b in zip(nb.utt_off[:-1], nb.utt_off[1:])]
+        self.idx = np.concatenate(keep) if keep else np.zeros(0, np.int64)
+        self.table = cnet.merge_nbest([[nb.hyp_words(int(h)).tolist() for h in hs] for hs in keep], mode, device)
+        dev = self.dev = self.table.device
+        self.inv = _dev(np.asarray(list(self.table._vocab) + [0], np.int32), torch.int32, dev)
+        roff = np.zeros(nb.n_utt + 1, np.int32)
+        roff[1:] = np.cumsum([len(r) for r in nb.refs])
+        self.d_rc, self.d_ro = _dev(np.concatenate(nb.refs), torch.int32, dev), _dev(roff, torch.int32, dev)
+        self.total = int(roff[-1])
+        self.one_off = np.arange(nb.n_utt + 1, dtype=np.int32)          # one decode per utterance
+        self.d_one = _dev(self.one_off, torch.int32, dev)
+        so = torch.from_numpy(self.table.slot_off.astype(np.int64)).to(dev)
+        n_slot = int(self.table.slot_off[-1])
+        utt = torch.repeat_interleave(torch.arange(nb.n_utt, device=dev), so[1:] - so[:-1])
+        self.slot_pos, self.slot_utt = torch.arange(n_slot, device=dev) - so[utt], utt
+
+    def weights(self, lm, weight: float, scale: float) -> np.ndarray:
+        nb, t = self.nb, self.table
+        lm = lm.cpu().numpy() if isinstance(lm, torch.Tensor) else np.asarray(lm)
+        return self.cnet.consensus_weights(np.asarray(nb.am)[self.idx], lm[self.idx], nb.hyp_len()[self.idx],
+                                           t.utt_off, weight, scale)
+
+    def decode(self, w: np.ndarray):
+        """(corpus edits, decoded id lists) of the vote under weights ``w``."""
+        lib, nb, dev = _lib.load(), self.nb, self.dev
+        _, _, _, dec, dlen = self.table.vote_device(torch.from_numpy(np.ascontiguousarray(w, np.float64)))
+        dlen = dlen[:nb.n_utt].to(torch.int64)
+        n_slot = self.slot_pos.numel()
+        flat = self.inv[dec[:n_slot][self.slot_pos < dlen[self.slot_utt]].to(torch.int64)]
+        soff = torch.zeros(nb.n_utt + 1, dtype=torch.int32, device=dev)
+        soff[1:] = torch.cumsum(dlen, 0)
+        chars = torch.cat([flat, torch.zeros(1, dtype=torch.int32, device=dev)]).contiguous()
+        ed = torch.empty(max(nb.n_utt, 1), dtype=torch.int32, device=dev)
+        _lib.check(lib.rs_ref_edit(_lib.ptr(chars), _lib.ptr(soff), _lib.ptr(self.d_one), _lib.ptr(self.d_rc),
+                                   _lib.ptr(self.d_ro), nb.n_utt, _lib.ptr(ed), _lib.stream_ptr(dev)))
+        first = torch.zeros(1, nb.n_utt, dtype=torch.int32, device=dev)
+        edits = int(corpus_edits(ed, self.one_off, first).cpu()[0])
+        so, fl = soff.cpu().numpy(), flat.cpu().numpy()
+        return edits, [fl[a:b] for a, b in zip(so[:-1], so[1:])]
+
+
+def consensus_decode(nb: NBest, lm, weight: float, scale: float = 1.0, n_best: int = 1 << 30, mode: str = "exact",
+                     device=0) -> Tuple[float, List[np.ndarray]]:
+    """Confusion-network consensus decode: every hypothesis votes per slot with its softmax-normalised
+    fused score (cnet.consensus_weights); returns (corpus CER, decoded ids per utterance), the CER as
+    ``find_best_weight`` forms it (rs_ref_edit, rs_corpus_edits; sum of edits / sum of reference symbols)."""
+    c = _Consensus(nb, n_best, mode, device)
+    edits, dec = c.decode(c.weights(lm, weight, scale))
+    return edits / c.total, dec
+
+
+def find_best_weight_consensus(nb: NBest, lm, n_best: int = 10, scale: float = 1.0, mode: str = "exact", device=0
+                               ) -> Tuple[float, float, np.ndarray]:
+    """The 101-weight grid of ``find_best_weight`` for the consensus decode: (best_weight, best_cer,
+    cer [W]); strict ``<`` keeps the first best weight.  The table is merged once and voted per weight."""
+    c = _Consensus(nb, n_best, mode, device)
+    grid = weight_grid("norm")
+    cers = np.asarray([c.decode(c.weights(lm, float(w), scale))[0] / c.total for w in grid])
+    best_i, best = 0, float("inf")
+    for i, v in enumerate(cers):
+        if v < best:
+            best, best_i = v, i
+    return float(grid[best_i]), float(best), cers
 
 
 def argmax_words(nb: NBest, idx: Sequence[int]) -> List[np.ndarray]:

@@ -350,6 +350,59 @@ int rs_align(const int32_t* d_ref, const int32_t* d_ref_off, const int32_t* d_hy
              int32_t n_pairs, const int64_t* d_lab_off, uint8_t* d_lab, const int64_t* d_out_off, int8_t* d_ops,
              int32_t* d_ref_idx, int32_t* d_hyp_idx, int32_t* d_n, int32_t max_len, void* stream);
 
+/* ---- N-best confusion network (Nbest_Align/preprocess.py:41-64,92-139; CorrectBart/get_feature.py) ----
+ * Utterance u owns hypotheses d_utt_off[u] .. d_utt_off[u+1]) (N >= 1), the first being the top-1 of L1
+ * tokens.  A table of S slots x N columns holds, per column n, the index of a token inside hypothesis n
+ * or -1 for a gap ("*"); column 0 is the top-1.  All calls are asynchronous on `stream`, use no atomics
+ * and give the same bits on every run.
+ *
+ * rs_cn_merge — new_merge_alignments folded over hypotheses 2..N (preprocess.py:41-64,103-108), in
+ * closed form: hypothesis n places k[n][g] tokens in gap g of the top-1 (g = 0..L1) and a[n][g] against
+ * position g; gap g gives K[g] = max_n k[n][g] slots, then position g one slot.  In gap slot m column n
+ * holds the m-th token hypothesis n has there; else, in RS_CN_REFERENCE and for g < L1, a copy of
+ * a[n][g] when m < max_{n' < n} k[n'][g] (the reference's "*" branch appends the other alignment's entry
+ * without advancing it); else a gap.  RS_CN_EXACT leaves a gap for those copies, so every hypothesis
+ * token appears exactly once.
+ *   d_ref_idx, d_hyp_idx, d_out_off, d_n   rs_align outputs for the pairs (top-1, hypothesis n), pair
+ *                order utterance-major with n ascending: pair of (u, column c >= 1) is
+ *                d_utt_off[u] - u + c - 1
+ *   d_hyp_len    int32 [n_hyp] token counts; max_len = the longest (<= 4096, else RS_EUNSUP)
+ *   d_gap_off    int64 [n_utt + 1], K of utterance u at d_K[d_gap_off[u] .. + L1 + 1)
+ * Two launches.  Count (d_src == NULL): writes d_K and d_n_slots[u] = S.  The caller forms
+ * d_slot_off int32 [n_utt + 1] (prefix sum of S) and d_cell_off int64 [n_utt + 1] (prefix sum of S * N).
+ * Fill (d_src != NULL): reads d_K, writes d_src[d_cell_off[u] + slot * N + n]; nothing is written at or
+ * beyond src_cap cells, and an utterance whose d_slot_off does not match its counts is left unwritten. */
+#define RS_CN_REFERENCE 0
+#define RS_CN_EXACT 1
+int rs_cn_merge(const int32_t* d_ref_idx, const int32_t* d_hyp_idx, const int64_t* d_out_off, const int32_t* d_n,
+                const int32_t* d_utt_off, const int32_t* d_hyp_len, int32_t n_utt, int32_t max_len,
+                const int64_t* d_gap_off, int32_t* d_K, int32_t* d_n_slots, const int32_t* d_slot_off,
+                const int64_t* d_cell_off, int32_t* d_src, int64_t src_cap, int32_t mode, void* stream);
+/* rs_cn_oracle — the search of preprocess.py:112-139 (every combination, jiwer.cer, tokens.index) as a DP.
+ * d_tok / d_hyp_off: the hypotheses' token ids (>= 0); d_ref / d_ref_off int32 [n_utt + 1]: one
+ * transcript per utterance, as token ids of the same vocabulary.  d_dist[u] = the minimum, over every
+ * path that picks one distinct entry per slot, of the token-level Levenshtein distance between the
+ * transcript and the path without its gaps.  d_label[d_slot_off[u] + s] = the lowest column holding the
+ * picked entry; among all minimum-distance paths the lexicographically smallest label vector.
+ * d_E: int32 scratch of (S + 1) * (len(ref) + 1) per utterance at d_e_off[u] (int64).
+ * Limits: max_n (most hypotheses of an utterance) <= 1024, max_ref (longest transcript) <= 4096, else
+ * RS_EUNSUP. */
+int rs_cn_oracle(const int32_t* d_src, const int32_t* d_slot_off, const int64_t* d_cell_off,
+                 const int32_t* d_utt_off, const int32_t* d_tok, const int32_t* d_hyp_off, int32_t n_utt,
+                 int32_t max_n, const int32_t* d_ref, const int32_t* d_ref_off, int32_t max_ref,
+                 const int64_t* d_e_off, int32_t* d_E, int32_t* d_dist, int32_t* d_label, void* stream);
+/* rs_cn_vote — ROVER-style vote per slot (no counterpart in the reference, which stops at the labels).
+ * A slot's candidates are its distinct entries, the gap being one; a candidate's mass is the float64 sum
+ * of d_w[hypothesis] over the columns holding it, added in ascending column order; the largest mass
+ * wins, ties go to the candidate whose first column is lowest.  Per slot: d_win_tok (token id, -1 = gap),
+ * d_win_col (the winner's first column), d_share (mass / sum of the utterance's weights, added in
+ * ascending column order).  The decode without gaps of utterance u is d_dec[d_slot_off[u] .. + d_dec_len[u]).
+ * max_n <= 1024, else RS_EUNSUP. */
+int rs_cn_vote(const int32_t* d_src, const int32_t* d_slot_off, const int64_t* d_cell_off,
+               const int32_t* d_utt_off, const int32_t* d_tok, const int32_t* d_hyp_off, int32_t n_utt,
+               int32_t max_n, const double* d_w, int32_t* d_win_tok, int32_t* d_win_col, double* d_share,
+               int32_t* d_dec, int32_t* d_dec_len, void* stream);
+
 /* ---- RescoreBert training (RescoreBert/main.py:82-229) ---------------------------------
  * A trainer holds fp32 parameters (HF keys as for rs_model; bert.pooler.* is accepted and
  * ignored — RescoreBert's loss never reaches it), their gradients and AdamW moments.
