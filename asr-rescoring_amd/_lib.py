@@ -71,6 +71,8 @@ _SIGS = {
     "rs_pll_score_spans": (ctypes.c_int, [P, P, P, I32, P, P, P, P, P, P, P]),
     "rs_pll_score_sets": (ctypes.c_int, [P, P, P, I32, P, P, P, P, P, P]),
     "rs_masked_logprob_multi": (ctypes.c_int, [P, P, P, I32, P, P, P, P, P]),
+    # (m, d_ids, h_seq_off, n_seq, h_q_off, h_qpos, h_c_off, h_cand, d_out, stream)
+    "rs_masked_logprob_cands": (ctypes.c_int, [P, P, P, I32, P, P, P, P, P, P]),
     "rs_masked_logprob": (ctypes.c_int, [P, P, P, P, P, I32, P, P]),
     "rs_masked_topk": (ctypes.c_int, [P, P, P, P, I32, I32, P, P, P]),
     "rs_pll_topk": (ctypes.c_int, [P, P, P, I32, I32, P, P, P, P, P]),
@@ -151,6 +153,8 @@ _DEBUG_SIGS = {
     "rs_debug_decoder": (CI, [P, P, P, P, CI, CI, CI, CI, CI, P, P, P, P, P]),
     # rs_debug_decoder's arguments up to out, then (k, cand, top_id, top_lp, stream)
     "rs_debug_decoder_topk": (CI, [P, P, P, P, CI, CI, CI, CI, CI, P, P, P, P, CI, P, P, P, P]),
+    # (A, W, bias, M_pad, m_valid, vpad, vocab, K, part, c_off, cand_id, perm, cand_logit, out, stream)
+    "rs_debug_decoder_cands": (CI, [P, P, P, CI, CI, CI, CI, CI, P, P, P, P, P, P, P]),
     # (qkv, qkv32, len, row, query, s0, s1, row0, H, heads, kx, qd, x32, stats, g, b, himg, ctxq, resq, stream)
     "rs_debug_attention_query": (CI, [P, CI, P, P, P, CI, CI, CI, CI, CI, CI, P, P, P, P, P, P, P, P, P]),
     # (himg, tq, wkf, wvt, bv, len, row, query, s0, s1, row0, H, heads, kx, work, work_bytes, ctxq, resq, stream)

@@ -9,6 +9,7 @@
   python -m asr_rescoring_amd.cli rmbr        --config CER.yaml      # RMBR/main.py (utility: cer / bertscore)
   python -m asr_rescoring_amd.cli nbest_align --config align.yaml    # Nbest_Align/preprocess.py (features + oracle)
   python -m asr_rescoring_amd.cli consensus   --config rescore.yaml  # confusion-network consensus decode
+  python -m asr_rescoring_amd.cli consensus_lm --config rescore.yaml # ... with masked-LM scores per contested slot
 
 Differences forced by the offline image (no model hub): ``model.bert`` cannot be fetched,
 so weights come from ``checkpoint_path`` (an HF-keyed state_dict, loaded with
@@ -760,6 +761,67 @@ def consensus(cfg) -> Dict[str, float]:
     return res
 
 
+def consensus_lm(cfg) -> Dict[str, float]:
+    """The consensus decode with the masked LM consulted at every contested top-1 position
+    (rerank.consensus_decode_lm).  Inputs: the model keys of ``mlm_pll`` (``checkpoint_path`` or
+    ``random_init_seed``, ``model.vocab``, ``precision``, ``max_rows``) and, per split (dev, test), the files of
+    ``rescore``: ``{split}_hyps_text_path``, ``{split}_ref_text_path``, ``{split}_am_path`` and the LM score JSON
+    ``{split}_lm_path``.  Hypotheses and transcripts are tokenised by the model's tokenizer, so the CER
+    counts its tokens (characters for CJK).  Keys: ``slot_lm_weight`` (a fixed lam in [0, 1]) or
+    ``slot_lm_grid`` (a list: the best lam on dev, default rerank.LAM_GRID); ``consensus_weight`` (the fusion
+    weight; absent: the best consensus weight on dev), ``consensus_scale`` (1.0), ``n_best``.  Logged to
+    output_path/consensus_lm.log, returned and written to consensus_lm.json."""
+    from . import rerank
+    from .scorer import PLLScorer
+    os.makedirs(cfg.output_path, exist_ok=True)
+    log = _logger(os.path.join(cfg.output_path, "consensus_lm.log"))
+    log.info(str(cfg))
+    n_best, dev_id = cfg.n_best, _dev(cfg)
+    scale = float(get(cfg, "consensus_scale", 1.0))
+    texts = {sp: (_load(getattr(cfg, f"{sp}_hyps_text_path")), _load(getattr(cfg, f"{sp}_ref_text_path")))
+             for sp in ("dev", "test")}
+    tok = _tokenizer(cfg, [t for hyps, refs in texts.values() for h in hyps.values() for t in h.values()] +
+                     [t for _, refs in texts.values() for t in refs.values()])
+
+    def split_nb(prefix):
+        hyps, refs = texts[prefix]
+        am, lm_j = _load(getattr(cfg, f"{prefix}_am_path")), _load(getattr(cfg, f"{prefix}_lm_path"))
+        items = {u: list(h.items())[:n_best] for u, h in hyps.items()}
+        nb = D.from_lists([[tok.encode_words(t) for _, t in it] for it in items.values()],
+                          [[float(am[u][h]) for h, _ in it] for u, it in items.items()],
+                          [tok.encode_words(refs[u]) for u in items], list(items))
+        nb.hyp_ids = [h for it in items.values() for h, _ in it]
+        return nb, np.asarray([lm_j[u][h] for u, it in items.items() for h, _ in it], np.float64)
+
+    scorer = PLLScorer(_weights(cfg, "mlm"), BERT_BASE, device=dev_id, max_rows=get(cfg, "max_rows", 65536),
+                       precision=get(cfg, "precision", "fp16x3"))
+    dev_nb, dev_lm = split_nb("dev")
+    w = get(cfg, "consensus_weight")
+    if w is None:
+        w = rerank.find_best_weight_consensus(dev_nb, dev_lm, n_best, scale, "exact", dev_id)[0]
+    w = float(w)
+    fixed = get(cfg, "slot_lm_weight")
+    if fixed is not None:
+        lam = float(fixed)
+        dev_cer = rerank.consensus_decode_lm(dev_nb, dev_lm, scorer, w, lam, scale, n_best, dev_id)[0]
+    else:
+        grid = [float(x) for x in (get(cfg, "slot_lm_grid") or rerank.LAM_GRID)]
+        lam, dev_cer, _ = rerank.find_best_weight_consensus_lm(dev_nb, dev_lm, scorer, w, grid, scale, n_best, dev_id)
+    test_nb, test_lm = split_nb("test")
+    test_cer, _, info = rerank.consensus_decode_lm(test_nb, test_lm, scorer, w, lam, scale, n_best, dev_id,
+                                                   return_info=True)
+    res = {"weight": w, "slot_lm_weight": lam, "dev_cer": dev_cer, "test_cer": test_cer,
+           "test_contested": info["n_contested"], "test_forwards": info["n_forwards"],
+           "consensus_dev_cer": rerank.consensus_decode(dev_nb, dev_lm, w, scale, n_best, "exact", dev_id)[0],
+           "consensus_test_cer": rerank.consensus_decode(test_nb, test_lm, w, scale, n_best, "exact", dev_id)[0]}
+    scorer.close()
+    for k, v in res.items():
+        log.info(f"{k}: {v}")
+        print(f"{k}: ", v)
+    D.json_saving(os.path.join(cfg.output_path, "consensus_lm.json"), res)
+    return res
+
+
 def _dev(cfg) -> int:
     d = str(get(cfg, "device", "cuda:0"))
     return int(d.split(":")[1]) if ":" in d else 0
@@ -776,7 +838,8 @@ def _logger(path):
 
 COMMANDS = {"mlm_pll": mlm_pll, "mlm_topk": mlm_topk, "mlm_finetune": mlm_finetune, "rescorebert": rescorebert,
             "rescorebert_train": rescorebert_train,
-            "rescore": rescore, "rmbr": rmbr, "nbest_align": nbest_align, "consensus": consensus}
+            "rescore": rescore, "rmbr": rmbr, "nbest_align": nbest_align, "consensus": consensus,
+            "consensus_lm": consensus_lm}
 
 
 def main(argv=None):

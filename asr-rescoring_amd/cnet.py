@@ -11,6 +11,7 @@ appears exactly once.  Tokens may be any hashable values except the gap ``"*"``.
 """
 from __future__ import annotations
 
+import math
 from typing import Hashable, List, Optional, Sequence
 
 import numpy as np
@@ -118,6 +119,118 @@ class SlotTable:
         inv = list(self._vocab)
         decoded = [[inv[t] for t in ws if t >= 0] for ws in self._split(win.cpu().numpy())]
         return decoded, self._split(col.cpu().numpy()), self._split(share.cpu().numpy())
+
+    def position_candidates(self, min_distinct: int = 2):
+        """The contested top-1 positions of an ``exact`` table: every slot whose column 0 is a top-1 token
+        (not a gap) and that holds at least ``min_distinct`` distinct non-gap entries.  Per such slot
+        ``(utterance, slot, g, tokens, cols)``: g the token's position in the top-1, the distinct non-gap
+        tokens in order of their first column, and those first columns.  A slot whose hypotheses agree
+        needs no language-model forward."""
+        if self.mode != "exact":
+            raise ValueError("position_candidates needs the exact table (every token appears once)")
+        out = []
+        for u, h in enumerate(self.hyps):
+            src = self.src_of(u)
+            if src.size == 0:
+                continue
+            # the slots worth a Python loop: a top-1 token and at least min_distinct distinct ids
+            width = max(max(len(t) for t in self._ids[u]), 1)
+            idm = np.full((len(h), width), -1, np.int64)
+            for n, t in enumerate(self._ids[u]):
+                idm[n, :len(t)] = t
+            tid = np.where(src >= 0, idm[np.arange(len(h))[None, :], np.maximum(src, 0)], -1)
+            srt = np.sort(tid, axis=1)
+            distinct = (srt[:, 0] >= 0).astype(np.int64) + ((srt[:, 1:] != srt[:, :-1]) & (srt[:, 1:] >= 0)).sum(1)
+            for s in np.nonzero((src[:, 0] >= 0) & (distinct >= min_distinct))[0].tolist():
+                row = src[s]
+                toks, cols = [], []
+                for n, i in enumerate(row):
+                    if i >= 0 and h[n][i] not in toks:
+                        toks.append(h[n][i])
+                        cols.append(n)
+                if len(toks) >= min_distinct:
+                    out.append((u, s, int(row[0]), toks, cols))
+        return out
+
+
+def _flat_weights(table: SlotTable, weights) -> np.ndarray:
+    n_hyp = int(table.utt_off[-1])
+    if weights is None:
+        return np.ones(n_hyp, np.float64)
+    if np.ndim(weights[0] if len(weights) else 0) == 0:
+        return np.asarray(weights, np.float64)
+    return np.concatenate([np.asarray(x, np.float64) for x in weights])
+
+
+def _lse(xs) -> float:
+    mx = max(xs)
+    return mx + math.log(sum(math.exp(x - mx) for x in xs))
+
+
+def slot_lm_vote(table: SlotTable, weights, slot_lp, lam: float):
+    """``SlotTable.vote`` with a masked-LM opinion on the slots of ``slot_lp``: ``{(utterance, slot): one
+    log-prob per distinct non-gap token of the slot, in ``position_candidates`` order}``.  Host, float64.
+
+    Per slot with scores, masses as ``rs_cn_vote`` forms them (float64 sum of ``w`` over a candidate's
+    columns, ascending): T = its non-gap candidates with mass > 0, M their total,
+    ``s_c = (1 - lam) ln m_c + lam (lp_c - logsumexp_T lp)`` (``lam == 1``: the second term alone) and
+    ``m''_c = M exp(s_c - logsumexp_T s)``: the LM redistributes the tokens' mass inside the slot.  The gap
+    keeps its mass and its verdict: it wins exactly when it wins the plain vote (the LM has no score
+    for "no token here"); otherwise the winner is the largest ``m''_c``, equal ones by the lowest first
+    column.  Slots without scores, and slots whose token mass is 0, keep the plain vote.  ``lam == 0``
+    is ``table.vote(weights)`` itself.  Returns what ``vote`` returns."""
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError("lam must be in [0, 1]")
+    decoded, cols, shares = table.vote(weights)
+    if lam == 0 or not slot_lp:
+        return decoded, cols, shares
+    w = _flat_weights(table, weights)
+    cols = [c.copy() for c in cols]
+    shares = [x.copy() for x in shares]
+    changed = set()
+    for (u, s), lps in slot_lp.items():
+        h = table.hyps[u]
+        row = table.src_of(u)[s]
+        wu = w[table.utt_off[u]:table.utt_off[u + 1]]
+        first, mass = {}, {}
+        for n, i in enumerate(row):                     # ascending column order, like the kernel
+            t = h[n][i] if i >= 0 else GAP
+            if t not in first:
+                first[t] = n
+                mass[t] = 0.0
+            mass[t] += float(wu[n])
+        toks = [t for t in first if t != GAP]
+        if len(lps) != len(toks):
+            raise ValueError(f"slot ({u}, {s}): {len(lps)} log-probs for {len(toks)} distinct tokens")
+        plain_win = None
+        for t in first:
+            if plain_win is None or mass[t] > mass[plain_win]:
+                plain_win = t
+        T = [(t, float(lp)) for t, lp in zip(toks, lps) if mass[t] > 0.0]
+        if plain_win == GAP or not T:
+            continue
+        M = 0.0
+        for t, _ in T:
+            M += mass[t]
+        L = _lse([lp for _, lp in T])
+        sc = [lp - L if lam == 1 else (1.0 - lam) * math.log(mass[t]) + lam * (lp - L) for t, lp in T]
+        Ls = _lse(sc)
+        best = None
+        for (t, _), x in zip(T, sc):
+            m2 = M * math.exp(x - Ls)
+            if best is None or m2 > best[0]:
+                best = (m2, t)
+        total = 0.0
+        for x in wu:
+            total += float(x)
+        cols[u][s] = first[best[1]]
+        shares[u][s] = best[0] / total
+        changed.add(u)
+    for u in changed:
+        h = table.hyps[u]
+        src = table.src_of(u)
+        decoded[u] = [h[c][src[s][c]] for s, c in enumerate(cols[u]) if src[s][c] >= 0]
+    return decoded, cols, shares
 
 
 def merge_nbest(hyps_per_utt: Sequence[Sequence[Sequence[Hashable]]], mode: str = "exact", device=0, *,

@@ -25,6 +25,8 @@ enum EpiKind {
                         //   (split-operand residual blocks; row statistics exchanged between the
                         //   column tiles of a row panel inside the launch: gemm_x3s_kernel)
     EPI_LSE_TOPK = 8,   // EPI_LSE, and per (row, 64-column slab) its best topk_k (logit, column) pairs
+    EPI_LSE_CAND = 9,   // EPI_LSE with, in place of the one label logit, the logit of every column of the
+                        //   row's candidate list (cand_off / cand_id / cand_logit)
 };
 
 struct EpiArgs {
@@ -68,6 +70,12 @@ struct EpiArgs {
     // then lower column); slots past a slab's valid columns hold (-inf, INT_MAX)
     float2* topk_cand;
     int topk_k;            // 1 .. TOPK_MAX
+    // EPI_LSE_CAND: row i owns cand_id[cand_off[i] .. cand_off[i + 1]), ascending (cand_off
+    // [m_valid + 1]); cand_logit[t] = the logit of column cand_id[t], stored where that column is a
+    // valid one (< n_valid), so an id outside [0, n_valid) leaves the launcher's preset
+    const int* cand_off;
+    const int* cand_id;
+    float* cand_logit;
 };
 constexpr int TOPK_MAX = 16;         // == RS_TOPK_MAX (rescore.h)
 constexpr int TOPK_SUB_ROWS = 2048;  // rows per decoder launch of the top-k form (bounds topk_cand)
@@ -421,6 +429,42 @@ hipError_t launch_mlm_decoder_topk(const MlmDecoder& d, const MlmTopk& t, hipStr
             return e;
     }
     return wrap(false, [&] { return launch_lse_finalize(d.part, n_parts, d.llog, d.m_valid, d.out, st); });
+}
+// The same decoder with a caller-chosen list of columns per row (no label): row i owns entries
+// [c_off[i], c_off[i + 1]) of cand_id, sorted ascending (duplicates are separate entries), and
+// out[perm[t]] = logit of column cand_id[t] - logsumexp of row i, the logsumexp formed by
+// lse_finalize's expression from the same slab pairs: the value is bit for bit what
+// launch_mlm_decoder gives the row with that column as its label.  An id outside [0, vocab) yields
+// -inf.  Three launches: the -inf preset of cand_logit [n_c], the EPI_LSE_CAND GEMM, the finalise.
+// d.tok / sm / lab / llog / out are not used.
+// The launch may be one chunk of a longer list: its rows' entries are [t0, t0 + n_c) of cand_id / perm,
+// c_off holds those absolute entry numbers, and only cand_logit is the chunk's own.
+struct MlmCands {
+    const int* c_off;      // [m_valid + 1] device, ascending, c_off[0] == t0, c_off[m_valid] == t0 + n_c
+    const int* cand_id;    // device, entry t at cand_id[t]
+    const int* perm;       // device: the output index of entry t
+    int t0, n_c;
+    float* cand_logit;     // [n_c] workspace: entry t at cand_logit[t - t0]
+    float* out;            // entry t at out[perm[t]]
+};
+hipError_t launch_fill_f32(float* p, size_t n, float v, hipStream_t st);
+hipError_t launch_cand_finalize(const float2* part, int n_parts, const float* cand_logit, const int* c_off,
+                                const int* perm, int rows, float* out, hipStream_t st);
+template <class Wrap>
+hipError_t launch_mlm_decoder_cands(const MlmDecoder& d, const MlmCands& c, hipStream_t st, Wrap&& wrap) {
+    if (c.n_c < 0 || c.t0 < 0) return hipErrorInvalidValue;
+    if (hipError_t e = wrap(false, [&] { return launch_fill_f32(c.cand_logit, (size_t)c.n_c, -INFINITY, st); })) return e;
+    if (c.n_c > 0 && (!c.cand_id || !c.perm || !c.cand_logit || !c.out)) return hipErrorInvalidValue;
+    float* const logit0 = c.n_c ? c.cand_logit - c.t0 : nullptr;   // indexed by the absolute entry number, from t0 on
+    EpiArgs ep{};
+    ep.bias = d.bias; ep.m_valid = d.m_valid; ep.n_valid = d.vocab; ep.lse_part = d.part;
+    ep.n_parts = d.vpad / 64; ep.cand_off = c.c_off; ep.cand_id = c.cand_id; ep.cand_logit = logit0;
+    const int al = gemm_row_align(), m_pad = (d.m_valid + al - 1) / al * al;
+    if (hipError_t e = wrap(true, [&] { return launch_gemm(EPI_LSE_CAND, d.A, d.W, m_pad, d.vpad, d.K, ep, st, 0); }))
+        return e;
+    return wrap(false, [&] {
+        return launch_cand_finalize(d.part, d.vpad / 64, logit0, c.c_off, c.perm, d.m_valid, c.out, st);
+    });
 }
 hipError_t launch_cls_linear(const float* h, int rows, int H, const float* w, const float* b,
                              float* out, hipStream_t st);

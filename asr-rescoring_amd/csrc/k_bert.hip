@@ -8,6 +8,8 @@
 //                  (MLM_PLL/main.py:101-105)
 //  topk_merge      merges the decoder epilogue's per-slab (logit, column) candidates into a row's
 //                  k best tokens and their log-probs (the same row before the label gather)
+//  cand_finalize   the candidate form's merge: the log-prob of every column of a row's candidate list
+//                  (the same row, the label gather at a caller-chosen set of columns)
 //  cls_linear      RescoreBert Linear(H, 1) on the CLS state (RescoreBert/model.py:19-20)
 //  segsum_f64      per-hypothesis PLL, float64, in row order (MLM_PLL/main.py:106-107)
 //
@@ -386,6 +388,36 @@ lse_finalize_kernel(const float2* __restrict__ part, int n_parts, const float* _
     if (lane == 0) out[row] = ll[row] - (mx + logf(sm));
 }
 
+// The candidate form's finalise (EPI_LSE_CAND): out[perm[t]] = cand_logit[t] - logsumexp(row) for the
+// entries t of the row's list [c_off[row], c_off[row + 1]).  One wave per row; mx and sm are
+// lse_finalize_kernel's loops and the subtraction its expression, statement for statement, so a
+// candidate's log-prob equals that kernel's output for the same column as label, bit for bit.  A
+// row with an empty list writes nothing.
+__global__ void __launch_bounds__(256)
+cand_finalize_kernel(const float2* __restrict__ part, int n_parts, const float* __restrict__ cl,
+                     const int* __restrict__ c_off, const int* __restrict__ perm, int rows, float* __restrict__ out) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    const int t0 = c_off[row], t1 = c_off[row + 1];
+    if (t0 >= t1) return;
+    const float2* p = part + (size_t)row * n_parts;
+    float mx = -INFINITY;
+    for (int k = lane; k < n_parts; k += 64)
+        if (p[k].y > 0.f) mx = fmaxf(mx, p[k].x);
+    mx = wave_max(mx);
+    float sm = 0.f;
+    for (int k = lane; k < n_parts; k += 64)
+        if (p[k].y > 0.f) sm += p[k].y * __expf(p[k].x - mx);
+    sm = wave_sum(sm);
+    for (int t = t0 + lane; t < t1; t += 64) out[perm[t]] = cl[t] - (mx + logf(sm));
+}
+
+__global__ void fill_f32_kernel(float* __restrict__ p, size_t n, float v) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) p[i] = v;
+}
+
 // Merges a row's n_parts x k slab candidates (EPI_LSE_TOPK: (logit, column bits), unused slots
 // (-inf, INT_MAX)) into its k best, in the epilogue's total order — larger logit first, the lower
 // column among equal logits — so the result does not depend on the slab a column fell in.  One wave
@@ -640,6 +672,20 @@ hipError_t launch_lse_finalize(const float2* part, int n_parts, const float* lab
     return hipGetLastError();
 }
 
+hipError_t launch_fill_f32(float* p, size_t n, float v, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(fill_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p, n, v);
+    return hipGetLastError();
+}
+
+hipError_t launch_cand_finalize(const float2* part, int n_parts, const float* cand_logit, const int* c_off,
+                                const int* perm, int rows, float* out, hipStream_t st) {
+    if (rows <= 0) return hipSuccess;
+    hipLaunchKernelGGL(cand_finalize_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, part, n_parts, cand_logit, c_off,
+                       perm, rows, out);
+    return hipGetLastError();
+}
+
 hipError_t launch_topk_merge(const float2* part, int n_parts, const float2* cand, int k, int rows, int* top_id,
                              float* top_lp, hipStream_t st) {
     if (rows <= 0) return hipSuccess;
@@ -699,6 +745,42 @@ extern "C" int rs_debug_decoder_topk(const void* A, const void* W, const float* 
                        (float2*)part, llog, out};
     const MlmTopk t{k, (float2*)cand, top_id, top_lp};
     const hipError_t e = launch_mlm_decoder_topk(d, t, (hipStream_t)stream, [](bool, auto&& launch) { return launch(); });
+    return e == hipSuccess ? 0 : -2;
+}
+
+// Test entry (not part of the scoring path): the candidate form of the decoder as head_mlm runs it
+// (launch_mlm_decoder_cands).  A / W / bias / M_pad / m_valid / vpad / vocab / K / part as
+// rs_debug_decoder; c_off [m_valid + 1], cand_id / perm [n_c] (n_c = c_off[m_valid]) device int32,
+// row i's ids ascending and perm a permutation of [0, n_c); the caller's cand_logit [n_c] and the
+// output out [n_c].  c_off and perm are read back and checked (ascending from 0; perm inside
+// [0, n_c)), so a malformed list is -1 and nothing is launched.  Synchronises the stream first.
+extern "C" int rs_debug_decoder_cands(const void* A, const void* W, const float* bias, int M_pad, int m_valid, int vpad,
+                                      int vocab, int K, void* part, const int* c_off, const int* cand_id, const int* perm,
+                                      float* cand_logit, float* out, void* stream) {
+    if (!A || !W || !bias || !part || !c_off) return -1;
+    if (m_valid <= 0 || M_pad != (m_valid + 255) / 256 * 256 || vpad <= 0 || vpad % 128 || vocab <= 0 || vocab > vpad ||
+        K <= 0 || K % 64)
+        return -1;
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<int> off((size_t)m_valid + 1);
+    if (hipStreamSynchronize(st) != hipSuccess ||
+        hipMemcpy(off.data(), c_off, off.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+        return -2;
+    if (off[0] != 0) return -1;
+    for (int i = 0; i < m_valid; ++i)
+        if (off[i + 1] < off[i]) return -1;
+    const int n_c = off[m_valid];
+    if (n_c > 0) {
+        if (!cand_id || !perm || !cand_logit || !out) return -1;
+        std::vector<int> pm((size_t)n_c);
+        if (hipMemcpy(pm.data(), perm, pm.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return -2;
+        for (int t = 0; t < n_c; ++t)
+            if (pm[t] < 0 || pm[t] >= n_c) return -1;
+    }
+    const MlmDecoder d{(const f16*)A, (const f16*)W, bias, m_valid, vpad, vocab, K, nullptr, SeqMeta{}, 0, nullptr,
+                       (float2*)part, nullptr, nullptr};
+    const MlmCands c{c_off, cand_id, perm, 0, n_c, cand_logit, out};
+    const hipError_t e = launch_mlm_decoder_cands(d, c, st, [](bool, auto&& launch) { return launch(); });
     return e == hipSuccess ? 0 : -2;
 }
 

@@ -95,7 +95,8 @@ gemm_f16_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
     constexpr int WTM = BM / WM, WTN = BN / WN;
     // MFMA shape: 16x16x32 everywhere except the logsumexp epilogue, whose in-register row
     // reductions are written for the 32x32x16 accumulator layout
-    constexpr bool LSE = EPI == EPI_LSE || EPI == EPI_LSE_TOPK;   // the decoder forms
+    constexpr bool LSE = EPI == EPI_LSE || EPI == EPI_LSE_TOPK || EPI == EPI_LSE_CAND;   // the decoder forms
+    constexpr bool CAND = EPI == EPI_LSE_CAND;
     constexpr int MS = LSE ? 32 : 16;
     // non-temporal epilogue stores (st16) for the fp16 outputs only
     constexpr bool NT = EPI == EPI_BIAS_F16 || EPI == EPI_GELU_F16;
@@ -310,10 +311,39 @@ gemm_f16_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
         for (int j = 0; j < TN; ++j)
 #pragma unroll
             for (int g = 0; g < 4; ++g) bz[j][g] = *(const float4*)(ep.bias + cbase + j * 32 + 8 * g);
+        // EPI_LSE_CAND: entries [clo[i], cend[i]) of cand_id are row i's candidates at or after this
+        // slab's first column: a lower-bound search of the row's ascending list, the TM rows of the
+        // lane side by side (independent loads), so a slab without candidates pays log2(list length)
+        // steps and one load, whatever the list holds.  Rows >= m_valid get an empty range.
+        int clo[TM], cend[TM];
+        if constexpr (CAND) {
+            const int first = n0 + wn * WTN;
+            int chi[TM];
+#pragma unroll
+            for (int i = 0; i < TM; ++i) {
+                const int row = rbase + i * 32;
+                const bool ok = row < ep.m_valid;
+                clo[i] = ok ? ep.cand_off[row] : 0;
+                cend[i] = ok ? ep.cand_off[row + 1] : 0;
+                chi[i] = cend[i];
+            }
+            for (bool any = true; any;) {
+                any = false;
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+                    if (clo[i] < chi[i]) {
+                        const int mid = (clo[i] + chi[i]) >> 1;
+                        if (ep.cand_id[mid] < first) clo[i] = mid + 1;
+                        else chi[i] = mid;
+                        any = true;
+                    }
+            }
+        }
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
             const int row = rbase + i * 32;
-            const int lab = row < ep.m_valid ? ep.label[row] : -1;
+            int lab = -1;
+            if constexpr (!CAND) lab = row < ep.m_valid ? ep.label[row] : -1;
             float v[TN][16];
             float mx = -INFINITY;
 #pragma unroll
@@ -327,7 +357,8 @@ gemm_f16_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
                         const float x = col + e < ep.n_valid ? acc[i][j][4 * g + e] + b4[e] : -INFINITY;
                         v[j][4 * g + e] = x;
                         mx = fmaxf(mx, x);
-                        if (col + e == lab) ep.label_logit[row] = x;
+                        if constexpr (!CAND)
+                            if (col + e == lab) ep.label_logit[row] = x;
                     }
                 }
             mx = fmaxf(mx, __shfl_xor(mx, 32));
@@ -370,6 +401,26 @@ gemm_f16_kernel(const f16* __restrict__ A, const f16* __restrict__ W, int K, int
                         for (int r = 0; r < 16; ++r)
                             if (cbase + j * 32 + 8 * (r >> 2) + (r & 3) == wc) v[j][r] = -INFINITY;
                     if (fh == 0 && row < ep.m_valid) cq[t] = make_float2(wv, __int_as_float(wc));
+                }
+            }
+            if constexpr (CAND) {
+                // The row's candidates inside this slab's valid columns, in list order.  Column c sits
+                // in register v[j][4g + e] (32 j + 8 g + e == c - cbase) of the lane of the pair
+                // (lane, lane ^ 32) whose fh is bit 2 of the column: that lane takes it out with a
+                // statically indexed select (no scratch) and stores it.  Equal ids are consecutive
+                // entries, each stored.
+                const int first = n0 + wn * WTN, last = min(first + WTN, ep.n_valid);
+                for (int t = clo[i]; t < cend[i]; ++t) {
+                    const int c = ep.cand_id[t];
+                    if (c >= last) break;
+                    const int r = c - cbase;
+                    float x = 0.f;
+#pragma unroll
+                    for (int j = 0; j < TN; ++j)
+#pragma unroll
+                        for (int q = 0; q < 16; ++q)
+                            if (r == j * 32 + 8 * (q >> 2) + (q & 3)) x = v[j][q];
+                    if ((((c - first) >> 2) & 1) == fh) ep.cand_logit[t] = x;
                 }
             }
         }
@@ -1791,7 +1842,8 @@ hipError_t launch_t(const f16* A, const f16* W, int M_pad, int N_pad, int K, con
 //   * everything else (fp32 outputs, the residual epilogues, the decoder logsumexp): the pipelined
 //     256 x 256 (N % 256 == 0) or 256 x 128 kernel, 16x16x32 MFMA except the logsumexp epilogue
 //     (32x32x16), non-temporal stores for fp16 outputs (both decided inside gemm_f16_kernel);
-//     EPI_LSE_TOPK is EPI_LSE on the same two tiles with the per-slab candidate selection added.
+//     EPI_LSE_TOPK is EPI_LSE on the same two tiles with the per-slab candidate selection added,
+//     EPI_LSE_CAND with the caller's candidate columns stored in place of the label logit.
 // Measured-slower alternatives (tile configurations 2-7, 32x32x16 in the pipelined kernel, the
 // unstaggered persistent schedules, direct residual stores, ...) are recorded in profiles/r1_*;
 // their code paths were removed in round 4.
@@ -1916,6 +1968,9 @@ hipError_t launch_gemm(int epi, const f16* A, const f16* W, int M_pad, int N_pad
         case EPI_LSE_TOPK:
             if (!ep.topk_cand || ep.topk_k < 1 || ep.topk_k > TOPK_MAX) return hipErrorInvalidValue;
             return launch_epi<EPI_LSE_TOPK>(A, W, M_pad, N_pad, K, ep, st, tag);
+        case EPI_LSE_CAND:
+            if (!ep.cand_off) return hipErrorInvalidValue;
+            return launch_epi<EPI_LSE_CAND>(A, W, M_pad, N_pad, K, ep, st, tag);
         case EPI_BIAS_F32: return launch_epi<EPI_BIAS_F32>(A, W, M_pad, N_pad, K, ep, st, tag);
         case EPI_RESLN_F32: return launch_epi<EPI_RESLN_F32>(A, W, M_pad, N_pad, K, ep, st, tag);
     }

@@ -93,6 +93,9 @@ struct rs_model {
     DevBuf ctxq, resq, tq32, hq32, hq16, interq, lab, llog, part, rowlp_tmp;
     DevBuf meta;
     DevBuf topk_cand;           // top-k calls (topk_begin): topk_cand_bytes(vpad), from the first such call on
+    // candidate calls (rs_masked_logprob_cands), from the first such call on: the call's offsets,
+    // sorted ids and permutation (one upload), and the candidate logits of one chunk
+    DevBuf cand_meta, cand_logit;
     // rs_model_set_token_types: segment ids pending for the next encoder call, [type_n] device ints
     // parallel to its tokens (PendingTypes hands them to that call and clears them)
     const int32_t* type_next = nullptr;
@@ -103,6 +106,7 @@ struct rs_model {
     int* pinned_flag = nullptr;
     // metadata (run_all) and BERTScore plan uploads: rs_bertscore_recall does both in one call, and
     Staging stage_meta, stage_plan;   // a shared buffer would make it wait on the host in between
+    Staging stage_cand;               // rs_masked_logprob_cands: the candidate lists (before its stage_meta upload)
     // call ordering across streams: the end of the last call's work (any stream); a call on another
     // stream first makes its stream wait for it (CallOrder)
     hipEvent_t call_done = nullptr;
@@ -421,9 +425,20 @@ struct Call {
     int topk_k = 0;
     int32_t* topk_id = nullptr;
     float* topk_lp = nullptr;
+    // candidate request (query-list calls; cands_begin): head_mlm runs the candidate decoder form,
+    // out_rows then holds one float per candidate, in the caller's order
+    const struct CandLists* cands = nullptr;
     // multi-mask rows: several scored positions per sequence (seq_plan.h QueryList); the last layer
     // and the head then run one row per query, out_rows holds one float per query
     const QueryList* ql = nullptr;
+};
+
+// The candidate lists of a call, query q's at entries [off[q], off[q + 1]): ids sorted by (id,
+// original index) inside each list, perm the original (caller's) index of every entry.
+struct CandLists {
+    std::vector<int> off;                     // [n_q + 1] host
+    const int *d_off = nullptr, *d_id = nullptr, *d_perm = nullptr;   // their device copies (cand_meta)
+    float* d_logit = nullptr;                 // one chunk's candidate logits (cand_logit)
 };
 
 // The environment switches of one scoring call: read once (call_opts, at the top of run_all) and
@@ -728,6 +743,17 @@ struct ChunkCtx {
         LAUNCH_OTHER(launch_ln_rows(tq, nr, m->gt, m->bet, eps, H, hq32, nullptr, hq16, kx, st));
         const MlmDecoder d{hq16, m->wdec, m->bdec, nr, m->vpad, cf.vocab, kx * H, call.d_tok, sm, r0, m->lab.as<int>(),
                            m->part.as<float2>(), m->llog.as<float>(), call.out_rows + r0, mq ? &qm : nullptr};
+        if (call.cands) {
+            // the only fork of a candidate call: the decoder launcher, over the chunk's queries' lists
+            const CandLists& cl = *call.cands;
+            const int t0 = cl.off[r0], n_c = cl.off[r0 + nr] - t0;
+            const MlmCands cc{cl.d_off + r0, cl.d_id, cl.d_perm, t0, n_c, cl.d_logit, call.out_rows};
+            TRY_HIP(launch_mlm_decoder_cands(d, cc, st, [&](bool is_gemm, auto&& launch) {
+                ProfScope ps(m, st, is_gemm ? RS_K_DECODER : RS_K_OTHER, is_gemm ? 2.0 * nr * (double)cf.vocab * (kx * H) : 0);
+                return launch();
+            }));
+            return RS_OK;
+        }
         if (call.topk_k) {
             // the only fork of a top-k call: the decoder launcher (its GEMM runs in n_gemm sub-batches)
             const int k = call.topk_k, n_gemm = (ns + TOPK_SUB_ROWS - 1) / TOPK_SUB_ROWS;
@@ -891,6 +917,44 @@ int topk_begin(rs_model* m, int k, int32_t* d_top_id, float* d_top_lp, Call* cal
         return fail(RS_ENOMEM, "top-k candidate workspace (" + std::to_string(topk_cand_bytes(m->vpad)) + " bytes)");
     }
     call->topk_k = k; call->topk_id = d_top_id; call->topk_lp = d_top_lp;
+    return RS_OK;
+}
+
+// A candidate call (rs_masked_logprob_cands) after its offsets are checked: validates the ids, sorts
+// every query's list by (id, original index), uploads offsets, ids and permutation in one copy, and
+// makes sure of the candidate-logit workspace: the most candidates any run of s_cap consecutive
+// queries holds, which bounds every chunk (cut_rows_queries gives a chunk at most s_cap queries).
+int cands_begin(rs_model* m, hipStream_t st, const int32_t* h_c_off, const int32_t* h_cand, int n_q, CandLists* cl) {
+    const int n_c = h_c_off[n_q];
+    cl->off.assign(h_c_off, h_c_off + n_q + 1);
+    TRY_HIP(m->stage_cand.begin((size_t)n_q + 1 + 2 * (size_t)n_c));
+    int* off = m->stage_cand.p;
+    int *id = off + n_q + 1, *perm = id + n_c;
+    std::memcpy(off, h_c_off, ((size_t)n_q + 1) * 4);
+    for (int q = 0; q < n_q; ++q) {
+        const int a = h_c_off[q], b = h_c_off[q + 1];
+        for (int t = a; t < b; ++t) {
+            if (h_cand[t] < 0 || h_cand[t] >= m->cfg.vocab)
+                return fail(RS_EARG, "query " + std::to_string(q) + ": candidate " + std::to_string(t - a) + " is id " +
+                                         std::to_string(h_cand[t]) + ", outside [0, " + std::to_string(m->cfg.vocab) + ")");
+            perm[t] = t;
+        }
+        std::sort(perm + a, perm + b, [&](int x, int y) { return h_cand[x] != h_cand[y] ? h_cand[x] < h_cand[y] : x < y; });
+        for (int t = a; t < b; ++t) id[t] = h_cand[perm[t]];
+    }
+    if (m->max_rows == 0)
+        if (int r = reserve_impl(m, 65536)) return r;
+    int most = 0;
+    for (int q = 0; q < n_q; ++q) most = std::max(most, h_c_off[std::min<int64_t>((int64_t)q + m->s_cap, n_q)] - h_c_off[q]);
+    if (m->cand_logit.ensure(std::max<size_t>(most, 1) * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(RS_ENOMEM, "candidate workspace (" + std::to_string((size_t)most * 4) + " bytes)");
+    }
+    TRY_HIP(m->stage_cand.upload(m->cand_meta, (size_t)n_q + 1 + 2 * (size_t)n_c, st));
+    cl->d_off = m->cand_meta.as<int>();
+    cl->d_id = cl->d_off + n_q + 1;
+    cl->d_perm = cl->d_id + n_c;
+    cl->d_logit = m->cand_logit.as<float>();
     return RS_OK;
 }
 
@@ -1323,6 +1387,45 @@ int rs_masked_logprob_multi(rs_model* m, const int32_t* d_ids, const int32_t* h_
     return check_finite(m, st, d_out, ql.size(), "masked-token log-probability");
 }
 
+int rs_masked_logprob_cands(rs_model* m, const int32_t* d_ids, const int32_t* h_seq_off, int32_t n_seq,
+                            const int32_t* h_q_off, const int32_t* h_qpos, const int32_t* h_c_off, const int32_t* h_cand,
+                            float* d_out, void* stream) {
+    PendingTypes ty(m);
+    if (!m || !h_seq_off || !h_q_off || n_seq < 0 || (n_seq > 0 && !d_ids)) return fail(RS_EARG, "null argument");
+    if (n_seq == 0) return RS_OK;
+    if (int r = validate_sets(m)) return r;
+    if (int r = offsets_ok(h_q_off, n_seq, "q_off")) return r;
+    const int n_q = h_q_off[n_seq];
+    if (n_q > 0 && (!h_qpos || !h_c_off)) return fail(RS_EARG, "null argument");
+    if (n_q > 0)
+        if (int r = offsets_ok(h_c_off, n_q, "c_off")) return r;
+    const int n_c = n_q > 0 ? h_c_off[n_q] : 0;
+    if (n_c > 0 && (!h_cand || !d_out)) return fail(RS_EARG, "null argument");
+    Call call{MODE_MLM, d_ids, d_out};
+    if (int r = ty.take(h_seq_off[n_seq], &call)) return r;
+    hipStream_t st = (hipStream_t)stream;
+    CALL_ORDER(m, st);
+    SeqList sl;
+    QueryList ql;
+    for (int s = 0; s < n_seq; ++s) {
+        const int o = h_seq_off[s], T = h_seq_off[s + 1] - o;
+        const int n = h_q_off[s + 1] - h_q_off[s];
+        const int32_t* p = n ? h_qpos + h_q_off[s] : nullptr;
+        if (!positions_ok(p, n, 0, T - 1))
+            return fail(RS_EARG, "row " + std::to_string(s) + " (T = " + std::to_string(T) +
+                                     "): need at least one query position, strictly ascending, 0 <= p < T, got " +
+                                     std::to_string(n) + " [" + positions_text(p, n) + "]");
+        sl.push(o, T, -1, -1, 0, 0);
+        ql.push(p, n, 0);
+    }
+    CandLists cl;
+    if (int r = cands_begin(m, st, h_c_off, h_cand, n_q, &cl)) return r;
+    call.ql = &ql;
+    call.cands = &cl;
+    if (int r = run_all(m, st, call, sl)) return r;
+    return check_finite(m, st, d_out, (size_t)n_c, "masked-token log-probability");
+}
+
 int rs_masked_logprob(rs_model* m, const int32_t* d_ids, const int32_t* h_seq_off,
                       const int32_t* h_query, const int32_t* d_label, int32_t n_seq, float* d_out,
                       void* stream) {
@@ -1528,6 +1631,7 @@ void rs_model_destroy(rs_model* m) {
     for (void* p : m->allocs) (void)hipFree(p);
     for (DevBuf* b : {&m->xst, &m->xst1, &m->h16, &m->t32, &m->qkv, &m->ctx, &m->inter, &m->ctxq, &m->resq,
                       &m->tq32, &m->hq32, &m->hq16, &m->interq, &m->lab, &m->llog, &m->part, &m->topk_cand,
+                      &m->cand_meta, &m->cand_logit,
                       &m->rowlp_tmp, &m->meta, &m->emb, &m->plan, &m->flag, &m->lnx, &m->lncnt,
                       &m->lnerr})
         b->release();

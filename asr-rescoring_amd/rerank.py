@@ -12,6 +12,8 @@ Host mirrors of the reference functions (same names, argument meaning, tie rules
 * ``consensus_decode`` / ``find_best_weight_consensus`` — no reference counterpart: the per-slot vote
   over the N-best confusion network (``cnet``), every hypothesis weighted by the softmax of the fused
   score, scored by the same CER kernels; a third decoding rule beside argmax and MBR.
+* ``consensus_decode_lm`` / ``find_best_weight_consensus_lm`` — no reference counterpart: that vote with
+  the masked LM's log-probs of each contested slot's competing tokens mixed in (``cnet.slot_lm_vote``).
 
 Inputs are ``NBest`` (token/char ids); "characters" are symbols, as jiwer's CER splits text
 into characters (CJK: one token per character).
@@ -247,6 +249,107 @@ def find_best_weight_consensus(nb: NBest, lm, n_best: int = 10, scale: float = 1
         if v < best:
             best, best_i = v, i
     return float(grid[best_i]), float(best), cers
+
+
+LAM_GRID = (0.0, 0.1, 0.2, 0.3, 0.5, 0.7, 1.0)
+
+
+class _ConsensusLM(_Consensus):
+    """``_Consensus`` (exact table) plus the masked-LM log-probs of every contested top-1 position's
+    candidates: one row ``[CLS] top-1 [SEP]`` per position, that position replaced by [MASK] on the
+    device, all rows in one ``score_cands`` call.  Computed once per table, reused for every ``lam``."""
+
+    def __init__(self, nb: NBest, scorer, n_best: int, device):
+        if nb.token_type is not None:
+            raise ValueError("consensus_decode_lm takes plain hypothesis lists (no context pairs)")
+        super().__init__(nb, n_best, "exact", device)
+        self.scorer = scorer
+        self._lp = self._pcs = None
+
+    def rows(self):
+        """(contested positions, device ids, seq_off, qpos): one row per ``position_candidates`` entry, the
+        utterance's ``[CLS] top-1 [SEP]`` with position g + 1 replaced by [MASK] on the device."""
+        nb, dev = self.nb, self.scorer.device
+        if self._pcs is None:
+            self._pcs = self.table.position_candidates()
+        pcs = self._pcs
+        ho = np.asarray(nb.hyp_off, np.int64)
+        top = np.asarray(nb.utt_off, np.int64)[[u for u, *_ in pcs]]            # the top-1 hypothesis of each row
+        a, T = ho[top], ho[top + 1] - ho[top]
+        seq_off = np.zeros(len(pcs) + 1, np.int64)
+        seq_off[1:] = np.cumsum(T)
+        src = np.repeat(a - seq_off[:-1], T) + np.arange(seq_off[-1])           # row r, position t <- token a[r] + t
+        qpos = np.asarray([g + 1 for _, _, g, _, _ in pcs], np.int64)           # past [CLS]
+        d_rows = self.scorer._dev_tokens(nb.tokens)[torch.from_numpy(src).to(dev)]
+        d_rows[torch.from_numpy(seq_off[:-1] + qpos).to(dev)] = self.scorer.shape.mask_id
+        return pcs, d_rows, seq_off.astype(np.int32), qpos.astype(np.int32)
+
+    def slot_lp(self):
+        """({(utterance, slot): float32 log-probs in ``position_candidates`` order}, forwards)."""
+        if self._lp is not None:
+            return self._lp
+        pcs, d_rows, seq_off, qpos = self.rows()
+        if not pcs:
+            self._lp = ({}, 0)
+            return self._lp
+        c_off = np.zeros(len(pcs) + 1, np.int32)
+        c_off[1:] = np.cumsum([len(t) for _, _, _, t, _ in pcs])
+        cand = np.asarray([t for _, _, _, toks, _ in pcs for t in toks], np.int32)
+        lp = self.scorer.score_cands(d_rows, seq_off, np.arange(len(pcs) + 1, dtype=np.int32), qpos, c_off,
+                                     cand).cpu().numpy()
+        self._lp = ({(u, s): lp[c_off[i]:c_off[i + 1]] for i, (u, s, *_) in enumerate(pcs)}, len(pcs))
+        return self._lp
+
+    def edits_of(self, decoded) -> int:
+        """Corpus edits of one decode per utterance (id lists), as ``decode`` scores the vote's."""
+        lib, nb, dev = _lib.load(), self.nb, self.dev
+        soff = np.zeros(nb.n_utt + 1, np.int32)
+        soff[1:] = np.cumsum([len(d) for d in decoded])
+        flat = np.asarray([t for d in decoded for t in d] + [0], np.int32)
+        chars, d_so = _dev(flat, torch.int32, dev), _dev(soff, torch.int32, dev)
+        ed = torch.empty(max(nb.n_utt, 1), dtype=torch.int32, device=dev)
+        _lib.check(lib.rs_ref_edit(_lib.ptr(chars), _lib.ptr(d_so), _lib.ptr(self.d_one), _lib.ptr(self.d_rc),
+                                   _lib.ptr(self.d_ro), nb.n_utt, _lib.ptr(ed), _lib.stream_ptr(dev)))
+        first = torch.zeros(1, nb.n_utt, dtype=torch.int32, device=dev)
+        return int(corpus_edits(ed, self.one_off, first).cpu()[0])
+
+    def decode_lm(self, w: np.ndarray, lam: float):
+        """(corpus edits, decoded id lists) of ``cnet.slot_lm_vote`` under weights ``w``."""
+        if lam == 0:
+            return self.decode(w)
+        dec, _, _ = self.cnet.slot_lm_vote(self.table, w, self.slot_lp()[0], lam)
+        dec = [np.asarray(d, np.int32) for d in dec]
+        return self.edits_of(dec), dec
+
+
+def consensus_decode_lm(nb: NBest, lm, scorer, weight: float, lam: float, scale: float = 1.0, n_best: int = 1 << 30,
+                        device=0, return_info: bool = False):
+    """``consensus_decode`` (exact table) with the masked LM's opinion on every contested top-1 position:
+    ``scorer`` (a ``PLLScorer`` whose vocabulary ids are ``nb``'s symbols) scores each such slot's
+    competing tokens from one masked forward of the top-1 (``PLLScorer.score_cands``), and
+    ``cnet.slot_lm_vote`` mixes them into the slot's vote with weight ``lam`` in [0, 1].  ``lam == 0`` is
+    ``consensus_decode`` itself and runs no forward.  Returns (corpus CER, decoded ids per utterance) and,
+    with ``return_info``, a dict: ``n_forwards``, ``n_contested`` and ``slot_lp`` (the log-probs used)."""
+    c = _ConsensusLM(nb, scorer, n_best, device)
+    edits, dec = c.decode_lm(c.weights(lm, weight, scale), float(lam))
+    if not return_info:
+        return edits / c.total, dec
+    slot_lp, n_fwd = c.slot_lp() if lam != 0 else ({}, 0)
+    return edits / c.total, dec, {"n_forwards": n_fwd, "n_contested": len(c.rows()[0]), "slot_lp": slot_lp}
+
+
+def find_best_weight_consensus_lm(nb: NBest, lm, scorer, weight: float, lam_grid: Sequence[float] = LAM_GRID,
+                                  scale: float = 1.0, n_best: int = 10, device=0) -> Tuple[float, float, np.ndarray]:
+    """Sweeps ``lam`` over ``lam_grid`` at a fixed fusion ``weight``: (best_lam, best_cer, cer per lam);
+    strict ``<`` keeps the first best.  The table is merged and the LM scores computed once."""
+    c = _ConsensusLM(nb, scorer, n_best, device)
+    w = c.weights(lm, weight, scale)
+    cers = np.asarray([c.decode_lm(w, float(lam))[0] / c.total for lam in lam_grid])
+    best_i, best = 0, float("inf")
+    for i, v in enumerate(cers):
+        if v < best:
+            best, best_i = v, i
+    return float(lam_grid[best_i]), float(best), cers
 
 
 def argmax_words(nb: NBest, idx: Sequence[int]) -> List[np.ndarray]:

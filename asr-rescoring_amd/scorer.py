@@ -286,6 +286,46 @@ class PLLScorer(BertEngine):
         full[b_idx, t_idx] = out
         return full
 
+    def score_cands(self, ids, seq_off, q_off, qpos, c_off, cand, token_types=None) -> torch.Tensor:
+        """Candidate log-probs on ragged rows (``rs_masked_logprob_cands``): row s is tokens
+        ``ids[seq_off[s]:seq_off[s + 1]]`` (already masked), scored at positions
+        ``qpos[q_off[s]:q_off[s + 1]]`` (strictly ascending, at least one per row); query q's candidates
+        are the vocabulary ids ``cand[c_off[q]:c_off[q + 1]]`` (any order, duplicates allowed, the list
+        may be empty).  Returns float32 [n_c] on the device, ``log_softmax(logits[qpos_q])[cand[c]]`` in
+        the order of ``cand``: bitwise what ``rs_masked_logprob_multi`` gives with that id as the label."""
+        d_ids, off, n_seq = self._hyps(ids, seq_off)
+        qo, qp, co, cd = (np.ascontiguousarray(a, np.int32).reshape(-1) for a in (q_off, qpos, c_off, cand))
+        if len(qo) != n_seq + 1:
+            raise ValueError("q_off must have one entry per row plus one")
+        n_q = max(int(qo[-1]), 0) if n_seq else 0
+        if len(qp) != n_q or len(co) != n_q + 1:
+            raise ValueError("qpos must have q_off[-1] entries and c_off one more")
+        n_c = max(int(co[-1]), 0)
+        if len(cd) != n_c:
+            raise ValueError("cand must have c_off[-1] entries")
+        out = torch.empty(n_c, dtype=torch.float32, device=self.device)
+        d_type = self._set_types(token_types)      # noqa: F841
+        _lib.check(self.lib.rs_masked_logprob_cands(self.handle, _lib.ptr(d_ids), off.ctypes.data, n_seq, qo.ctypes.data,
+                                                    qp.ctypes.data, co.ctypes.data, cd.ctypes.data, _lib.ptr(out),
+                                                    _lib.stream_ptr(self.device)))
+        return out
+
+    def masked_logprob_cands(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, mask_pos, candidates,
+                             token_type_ids=None):
+        """``log_softmax(logits[b, mask_pos[b]])[candidates[b]]`` for a padded batch [B, T] (the form
+        ``masked_logprob`` takes), ``candidates`` a list of id lists, one per row.  Returns a list of
+        float32 device tensors, one per row, in the order of that row's list."""
+        d_ids, off, types = _ragged(input_ids, attention_mask, token_type_ids, self.device)
+        B = input_ids.shape[0]
+        if len(candidates) != B:
+            raise ValueError("candidates must hold one list per row")
+        mp = np.asarray([int(x) for x in mask_pos], np.int32)
+        c_off = np.zeros(B + 1, np.int32)
+        c_off[1:] = np.cumsum([len(c) for c in candidates])
+        cand = np.asarray([int(x) for c in candidates for x in c], np.int32)
+        out = self.score_cands(d_ids, off, np.arange(B + 1, dtype=np.int32), mp, c_off, cand, token_types=types)
+        return [out[c_off[b]:c_off[b + 1]] for b in range(B)]
+
     def masked_logprob(self, input_ids: torch.Tensor, attention_mask: torch.Tensor,
                        labels: torch.Tensor, mask_pos, token_type_ids=None) -> torch.Tensor:
         """``token_score`` of MLM_PLL/main.py:101-105 for a padded batch [B, T].

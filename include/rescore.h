@@ -232,6 +232,27 @@ int rs_pll_score_sets(rs_model* m, const int32_t* d_tok, const int32_t* h_hyp_of
 int rs_masked_logprob_multi(rs_model* m, const int32_t* d_ids, const int32_t* h_seq_off, int32_t n_seq,
                             const int32_t* h_q_off, const int32_t* h_qpos, const int32_t* d_label,
                             float* d_out, void* stream);
+/* rs_masked_logprob_multi with a candidate list per query in place of one label: the log-probability
+ * of every listed vocabulary id at the query's position, from the row's one forward (the decoder
+ * keeps the listed columns of the logit row it has formed; the [n_q, vocab] logits are never stored).
+ * No reference counterpart; the seam is the slot question of Nbest_Align/model.py:20-45.
+ *   h_c_off    int32 [n_q + 1] host     candidates of query q: h_cand[h_c_off[q] .. h_c_off[q+1]);
+ *                                       starts at 0, never descends (else RS_EARG); an empty list is
+ *                                       allowed and scores nothing
+ *   h_cand     int32 [n_c] host         vocabulary ids in any order, duplicates allowed (each entry gets
+ *                                       its value); an id outside [0, vocab) is RS_EARG with a message
+ *                                       naming the query
+ *   d_out      float32 [n_c]            d_out[c] = log_softmax(logits[qpos of c's query])[h_cand[c]], in
+ *                                       the caller's order
+ * d_out[c] equals, bit for bit, what rs_masked_logprob_multi returns for that query with h_cand[c] as
+ * its label; it does not depend on the query's other candidates, on the chunking (max_rows) or on
+ * the run.  Rows, queries, precision modes, chunking, rs_model_set_token_types, the range guard over
+ * d_out, deferred checks, call ordering and the RS_ESTATE / RS_EUNSUP cases are those of
+ * rs_masked_logprob_multi.  The candidate workspace (the call's lists and one chunk's logits) is
+ * allocated at the first such call and kept on the handle (RS_ENOMEM if it cannot be). */
+int rs_masked_logprob_cands(rs_model* m, const int32_t* d_ids, const int32_t* h_seq_off, int32_t n_seq,
+                            const int32_t* h_q_off, const int32_t* h_qpos, const int32_t* h_c_off,
+                            const int32_t* h_cand, float* d_out, void* stream);
 
 /* Top-k token candidates at masked positions: the model's k preferred vocabulary entries of a row
  * and their log-probabilities.  Reference seam: logits[range(B), mask_pos] of MLM_PLL/main.py:101-105
