@@ -17,7 +17,10 @@ Shapes: T = 3; 48, 49, 64, 65 (the staged-key boundaries of the neighbouring att
 fold kernel's own tile is 24 rows, so 48 / 49 is also its two / three tile edge); 512 (the model's
 longest); five sequences of T = 3, 24, 25, 130, 7 in one launch (n = 5 is no multiple of the GEMM
 tiles' 32 rows), the query at the first, last and an interior position; that chunk again with bk x 100,
-and with a scratch buffer of two sequences (the launcher's batches: 2 + 2 + 1).
+and with a scratch buffer of two sequences (the launcher's batches: 2 + 2 + 1).  The other hidden sizes
+the fold accepts, H = 256, 512, 1024 with heads = H / 64 (attn_fold_kernel<1>, <2>, <4>: 256 / 512 / 1024
+threads, 24 / 48 / 96 KiB of LDS), run T3, T49, chunk5 and chunk5-batches with the same reference,
+sentinel checks and bound.
 
 Through the scorer: RS_LASTFOLD=0 / 1 both within the golden test's bounds of tests/golden/
 pll_base.npz and not array-equal (the switch takes effect), also at max_rows = 512 (hypotheses cut
@@ -29,7 +32,8 @@ is not taken there).
 Measured on MI355X (printed per case, LASTFOLD lines): err 1.4e-6 .. 3.5e-6 with e32 1.7e-6 .. 2.6e-6,
 err / e32 0.79 .. 1.37, err / bound 0.20 .. 0.34 (the worst sequence of the chunk is its T = 3 one);
 bk x 100: the same err (3.5e-6, the kernels' bits do not depend on bk) against an e32 of 1.5e-5 (the
-unfolded float32 scores carry the large constant), err / bound 0.06.  Scorer on the fixture: PLL
+unfolded float32 scores carry the large constant), err / bound 0.06.  H 256 / 512 / 1024: err 3.1e-7 ..
+5.6e-6, err / e32 0.71 .. 2.07, err / bound 0.14 .. 0.52 (the worst: H 1024 chunk5).  Scorer on the fixture: PLL
 1.8e-7 / rows 1.4e-6 folded, 1.5e-7 / 1.2e-6 with RS_LASTFOLD=0 (bounds 1e-6 / 5e-6), the two within
 7.5e-8 (PLL) and 5.4e-7 (rows) of each other, the same figures at max_rows 512.
 """
@@ -62,13 +66,26 @@ CASES = {
 }
 
 
+# the other hidden sizes attention_fold_ok accepts (heads = H / 64): attn_fold_kernel<1>, <2>, <4>
+OTHER_H = (256, 512, 1024)
+OTHER_H_CASES = ("T3", "T49", "chunk5", "chunk5-batches")
+H_CASES = [(H, n) for n in CASES] + [(h, n) for h in OTHER_H for n in OTHER_H_CASES]
+H_CASE_IDS = [n if h == H else f"H{h}-{n}" for h, n in H_CASES]
+
+
 @pytest.fixture(scope="module")
 def fold_weights():
-    """Wk, bk, Wv, bv (fp32, shared by every case and left unchanged)."""
-    gen = torch.Generator().manual_seed(4242)
-    rn = lambda *s: torch.randn(*s, generator=gen)
-    return {"wk": (0.05 * rn(H, H)).contiguous(), "bk": (0.3 * rn(H)).contiguous(),
-            "wv": (0.05 * rn(H, H)).contiguous(), "bv": (0.3 * rn(H)).contiguous()}
+    """H -> Wk, bk, Wv, bv (fp32, shared by every case of that H and left unchanged)."""
+    made = {}
+
+    def get(H):
+        if H not in made:
+            gen = torch.Generator().manual_seed(4242)
+            rn = lambda *s: torch.randn(*s, generator=gen)
+            made[H] = {"wk": (0.05 * rn(H, H)).contiguous(), "bk": (0.3 * rn(H)).contiguous(),
+                       "wv": (0.05 * rn(H, H)).contiguous(), "bv": (0.3 * rn(H)).contiguous()}
+        return made[H]
+    return get
 
 
 def _layout(Ts, qs, gap=3):
@@ -86,6 +103,8 @@ def _unfolded(x, q, w, bk_scale, T, row, query, dtype):
     """softmax(q_h . K_h^T / 8) . V_h of sequences [1, len(T) - 1) with K, V projected for every row."""
     f = lambda t: t.numpy().astype(dtype)
     wk, wv, bk, bv = f(w["wk"]), f(w["wv"]), f(w["bk"]) * dtype(bk_scale), f(w["bv"])
+    H = wk.shape[0]
+    HEADS = H // 64
     out = np.zeros((len(T) - 2, H), dtype)
     for i, s in enumerate(range(1, len(T) - 1)):
         xs = x[row[s]:row[s] + T[s]].astype(dtype)
@@ -102,8 +121,10 @@ def _bits(t):
     return t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int16)
 
 
-@pytest.mark.parametrize("name", list(CASES))
-def test_fold_vs_float64_unfolded(name, fold_weights):
+@pytest.mark.parametrize("H,name", H_CASES, ids=H_CASE_IDS)
+def test_fold_vs_float64_unfolded(H, name, fold_weights):
+    HEADS = H // 64
+    fold_weights = fold_weights(H)
     Ts, qs, bk_scale, scratch = CASES[name]
     T, row, query, rows = _layout(Ts, qs)
     n, n_seq = len(Ts), len(T)
@@ -144,13 +165,13 @@ def test_fold_vs_float64_unfolded(name, fold_weights):
     err_s = np.abs(val - ref).max(axis=1)
     err = err_s.max()
     bound = 4 * max(e32, 2.0 ** -21 * np.abs(ref).max())
-    print(f"LASTFOLD {name}: err {err:.3e} (T of the worst sequence {Ts[int(err_s.argmax())]}) e32 {e32:.3e} "
+    print(f"LASTFOLD H{H} {name}: err {err:.3e} (T of the worst sequence {Ts[int(err_s.argmax())]}) e32 {e32:.3e} "
           f"err/e32 {err / max(e32, 1e-300):.2f} err/bound {err / bound:.3f}")
     qrow = torch.tensor([row[s] + query[s] for s in range(1, 1 + n)])
     assert torch.equal(resq[:n].cpu().double(), _unsplit2(himg[qrow], torch.float64)), "resq != hi + lo/64"
     again = run()
     assert torch.equal(_bits(ctxq), _bits(again[0])) and torch.equal(_bits(resq), _bits(again[1])), "run-to-run"
-    assert err <= bound, (name, err, e32, bound)
+    assert err <= bound, (H, name, err, e32, bound)
 
 
 def test_fold_rejects_bad_arguments():
